@@ -18,6 +18,11 @@ global frame index, so no pixel ever crosses xGMI).  Inputs are resident in HBM 
 region.  RCCL is used only where the batch split needs it: broadcast of the quantizer table and
 all-gather of per-rank checksums.  Rank 0 prints ONE JSON line.
 
+A plain run times the headline workload and nothing else: set-up, settle + W warm-up steps, the K timed steps, the
+reconstruction-error check, the line.  --full adds the legs that take runs of their own (copy yardstick, P_fine, the
+plain-allocation comparison, the device entropy stage, C4, cpu_baseline).  --dump-outputs DIR writes a fixed sample of
+what the last timed step computed (grids and decoded frames) as .npy files, so that two builds can be compared.
+
 --rehearse: the same launcher, rendezvous, broadcast, sharding, barrier/timing and gather code on the CPU with the
 gloo backend and NO codec work (there is no CPU codec in the product): what the CPU test suite runs to show that
 `python bench.py --gpus 2` starts two ranks and returns one line.  Its line carries "rehearsal": true and value null.
@@ -38,6 +43,8 @@ sys.path.insert(0, ROOT)
 
 SEED0 = 0x48474930
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec (guide: MI355X_MICROARCH.md, chip-level parameters)
+DUMP_SAMPLES = 1 << 22     # --dump-outputs: pixels per array (2 arrays x 4 Mi x 4 B of float32 = 32 MiB)
+DUMP_SEED = SEED0 + 0x44
 
 
 def table_quantizator(table, error):
@@ -143,6 +150,16 @@ def cpu_baseline(args, lut, gpu_check):
     return res
 
 
+def dump_positions(frames, pixels):
+    """Which pixels of each frame --dump-outputs writes: all of them when the frames fit DUMP_SAMPLES, else the same number
+    from every frame, one from each equal stretch of it, at offsets drawn from a generator seeded with DUMP_SEED.  They
+    depend on the frame count and size only, so two builds run with the same arguments write comparable arrays."""
+    per = max(1, min(pixels, DUMP_SAMPLES // frames))
+    stride = pixels // per
+    offsets = np.random.default_rng(DUMP_SEED).integers(0, stride, size=(frames, per))
+    return np.arange(per, dtype=np.int64) * stride + offsets
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -155,11 +172,18 @@ def parse_args(argv=None):
     ap.add_argument("--size", type=int, default=4096)
     ap.add_argument("--levels", type=int, default=4)
     ap.add_argument("--quant", default="medium")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-pfine", action="store_true", help="skip the P_fine (levels = 1) leg")
-    ap.add_argument("--no-c4", action="store_true", help="skip the C4 leg (one 16384x16384 frame, level 8, High)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the legs that take runs of their own: the copy yardstick, P_fine, "
+                         "the plain-allocation comparison, the device entropy stage, C4 and cpu_baseline (each can be "
+                         "skipped with the --no-* options below).  Without it the run times the headline workload only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed -- a fixed, seeded sample of the encoded "
+                         "grids and decoded frames -- as DIR/grid.npy and DIR/decoded.npy (float32; suffix _rank<r> when N > 1)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-pfine", action="store_true", help="with --full: skip the P_fine (levels = 1) leg")
+    ap.add_argument("--no-c4", action="store_true", help="with --full: skip the C4 leg (one 16384x16384 frame, level 8, High)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the timed steps and the copy yardstick: no P_fine leg, no plain-allocation comparison "
+                    help="with --full: only the timed steps and the copy yardstick: no P_fine leg, no plain-allocation comparison "
                          "(profiling passes: every k_*_tiles launch in the trace is then a launch of the headline workload)")
     ap.add_argument("--xgmi-scatter", action="store_true",
                     help="also time the labelled variant where all frames start and end on GPU 0 (scatter, code, gather)")
@@ -172,7 +196,10 @@ def parse_args(argv=None):
                          "(at most 6 ranks: the GPU boxes allow six processes on a card)")
     ap.add_argument("--rehearse", action="store_true",
                     help="CPU rehearsal of the multi-rank plumbing (gloo, no codec work, value null)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def shard_plan(args, world):
@@ -338,14 +365,18 @@ def run_rank(args):
             dist.destroy_process_group()
         return 0
 
+    # the frame stacks still hold the last timed step's grids and decoded frames: the legs below overwrite them
+    if args.dump_outputs:
+        codec.dump_outputs(args.dump_outputs, "_rank%d" % rank if world > 1 else "")
     enc_ms, dec_ms = codec.mean_ms()
-    copy_ms = codec.copy_ms() if rank == 0 else None
-    pfine = codec.p_fine() if rank == 0 and not (args.no_pfine or args.no_extras) else None
-    placement = codec.placement(compare=not args.no_extras) if rank == 0 else None
+    full = args.full
+    copy_ms = codec.copy_ms() if rank == 0 and full else None
+    pfine = codec.p_fine() if rank == 0 and full and not (args.no_pfine or args.no_extras) else None
+    placement = codec.placement(compare=full and not args.no_extras) if rank == 0 else None
     xgmi = codec.xgmi(dist, world, rank, fence, args.steps, G // world) if args.xgmi_scatter and dist is not None else None
-    entropy = codec.entropy_stage() if rank == 0 and world == 1 and not args.no_extras else None
+    entropy = codec.entropy_stage() if rank == 0 and world == 1 and full and not args.no_extras else None
 
-    c4 = codec.c4() if rank == 0 and world == 1 and not (args.no_extras or args.no_c4) else None
+    c4 = codec.c4() if rank == 0 and world == 1 and full and not (args.no_extras or args.no_c4) else None
 
     # ---- per-rank checks + stats gather (RCCL all-gather) ----
     # every rank's own view of its run, so that a multi-GPU line explains itself: how long plane placement took there and
@@ -389,11 +420,12 @@ def run_rank(args):
                          "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": round(dom_ms, 4),
                          "other_kernel": {"kernel": "k_%s_tiles" % ("dec" if dom == "encode" else "enc"),
                                           "achieved": round(alg_bytes / (min(enc_ms, dec_ms) * 1e-3) / 1e9, 1),
-                                          "avg_launch_ms": round(min(enc_ms, dec_ms), 4)},
-                         "copy_same_run": {"achieved": round(alg_bytes / (copy_ms * 1e-3) / 1e9, 1),
-                                           "avg_launch_ms": round(copy_ms, 4),
-                                           "note": "16-B/lane copy kernel moving the same bytes"}},
+                                          "avg_launch_ms": round(min(enc_ms, dec_ms), 4)}},
         }
+        if copy_ms is not None:
+            line["roofline"]["copy_same_run"] = {"achieved": round(alg_bytes / (copy_ms * 1e-3) / 1e9, 1),
+                                                 "avg_launch_ms": round(copy_ms, 4),
+                                                 "note": "16-B/lane copy kernel moving the same bytes"}
         line["build"] = stamp
         line["config"]["placement"] = placement
         line["config"]["per_rank"] = per_rank
@@ -409,7 +441,7 @@ def run_rank(args):
             line["entropy_stage"] = entropy
         if c4 is not None:
             line["c4"] = c4
-        if world == 1 and not args.no_cpu:
+        if world == 1 and full and not args.no_cpu:
             line["cpu_baseline"] = cpu_baseline(args, lut, codec.sample())
         emit(json.dumps(line))
     if dist is not None:
@@ -861,6 +893,18 @@ class Codec:
 
     def sample(self):
         return {"grid": self.grids[:2].cpu().numpy(), "out": self.outs[:2].cpu().numpy()}
+
+    def dump_outputs(self, out_dir, suffix=""):
+        """--dump-outputs: the encoded grids and the decoded frames as they stand, i.e. what the last step computed, at the
+        pixels dump_positions() picks: (frames, pixels) float32 per array."""
+        torch = self.torch
+        F, P = self.F, self.S * self.S
+        idx = torch.from_numpy(dump_positions(F, P)).to(self.dev)
+        os.makedirs(out_dir, exist_ok=True)
+        for name, t in (("grid", self.grids), ("decoded", self.outs)):
+            got = torch.gather(t.view(F, P), 1, idx).cpu().numpy().astype(np.float32)
+            np.save(os.path.join(out_dir, name + suffix + ".npy"), got)
+        del idx
 
     def close(self):
         del self.imgs, self.grids, self.outs

@@ -174,6 +174,57 @@ def test_four_ranks_share_one_device_with_scatter_and_gather(oracle):
         assert got == hashlib.sha256(want.tobytes()).hexdigest()[:16], "rank %d: the gathered frame is not the oracle's" % rank
 
 
+def test_plain_run_options_and_dump_positions():
+    """A plain run times the headline only (the extra legs are behind --full); --steps sets the timed steps and must be
+    positive; --dump-outputs samples fixed, in-bounds positions of every frame, 64 MB of float32 at most for two arrays."""
+    import bench
+    import numpy as np
+    args = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert args.full is False and args.dump_outputs is None and args.steps == 7 and args.warmup == 2
+    assert bench.parse_args(["--full", "--dump-outputs", "d"]).full is True
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+    for frames, size in ((512, 4096), (64, 4096), (3, 2048), (1, 16384), (2, 64)):
+        pos = bench.dump_positions(frames, size * size)
+        assert pos.shape[0] == frames and 2 * pos.size * 4 <= 64 * 2 ** 20
+        assert pos.min() >= 0 and pos.max() < size * size and (np.diff(pos, axis=1) > 0).all()
+        assert (pos == bench.dump_positions(frames, size * size)).all()
+    assert (bench.dump_positions(2, 64 * 64) == np.arange(64 * 64)).all()      # small outputs are written whole
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_dump_outputs_are_the_last_steps_results(oracle, tmp_path):
+    """`--dump-outputs DIR` writes the grids and decoded frames of the timed path at dump_positions(), which must be the
+    oracle's encode and decode of those frames; a plain line carries none of the --full legs, a --full line has them."""
+    import bench
+    import numpy as np
+    from conftest import SEED0
+    F, S = 3, 2048
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--frames", str(F), "--size", str(S), "--placement", "torch"]
+    r = subprocess.run([sys.executable, BENCH] + common + ["--dump-outputs", str(tmp_path / "out")],
+                       env=_env(), capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _one_line(r.stdout)
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["config"]["max_abs_err"] <= 20
+    assert not {"p_fine", "c4", "entropy_stage", "cpu_baseline"} & set(d) and "copy_same_run" not in d["roofline"]
+    assert "plain_torch_allocations" not in d["config"]["placement"]
+    pos = bench.dump_positions(F, S * S)
+    grid, dec = np.load(tmp_path / "out" / "grid.npy"), np.load(tmp_path / "out" / "decoded.npy")
+    assert grid.dtype == dec.dtype == np.float32 and grid.shape == dec.shape == pos.shape
+    lut = oracle.linear_lut(2)[0]
+    for f in range(F):
+        want = oracle.encode(oracle.synth(oracle.SYNTH_RAMP, SEED0 + 3, f, S, S), 4, lut)
+        assert (grid[f] == want.reshape(-1)[pos[f]]).all(), "frame %d: dumped grid is not the oracle's" % f
+        assert (dec[f] == oracle.decode(want, 4).reshape(-1)[pos[f]]).all(), "frame %d: dumped decode is not the oracle's" % f
+    r = subprocess.run([sys.executable, BENCH] + common + ["--full", "--no-c4"], env=_env(), capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _one_line(r.stdout)
+    assert {"p_fine", "entropy_stage", "cpu_baseline"} <= set(d) and "copy_same_run" in d["roofline"]
+    assert "plain_torch_allocations" in d["config"]["placement"]
+
+
 def test_traffic_record_is_tied_to_the_build(tmp_path, monkeypatch):
     """`roofline.traffic` comes from a committed rocprofv3 record; bench.py takes it only when the record was made on this
     workload AND on this build of the library (the hash over the library's sources recorded by tools/summarize_prof.py equals
