@@ -2,7 +2,8 @@
 // MI355X library.  Same subcommands, flags and defaults:
 //
 //   hgi encode -i <input> -o <output> [-l <level>=4] [-q lossless|low|medium|high = medium]
-//   hgi decode -i <input.hgi> -o <output>
+//   hgi decode -i <input.hgi> -o <output> [--region X,Y,W,H]
+//   (--region: only that window of the image is decoded and written -- no counterpart in the reference)
 //   hgi test <input> [-s <suffix>=""] [-l <level>=4] [-q <quantizator>=medium]
 //   (encode / test also take --entropy zlib|device|auto, default zlib: `device` has the GPU write the archive's DEFLATE stream
 //    as Huffman-coded literals -- same container, readable by the same readers; no counterpart in the reference)
@@ -157,6 +158,7 @@ struct Opts {
     std::string cmd, input, output, suffix;
     size_t level = 4;                                            // src/options.rs:54
     QuantizationLevel quant = QuantizationLevel::Medium;         // src/options.rs:62
+    std::string region;   // --region X,Y,W,H (decode): the window to decode; no reference flag
     int entropy = 0;   // --entropy zlib (0, the reference's writer) | device (1: the GPU's entropy stage) | auto (2: device unless an LZ77 probe says zlib wins); no reference flag
 };
 
@@ -183,6 +185,7 @@ Opts parse(int argc, char **argv)
         else if (a == "-l" || a == "--level") o.level = std::stoul(next());
         else if (a == "-q" || a == "--quantizator") o.quant = parse_level(next());
         else if (a == "-s" || a == "--suffix") o.suffix = next();
+        else if (a == "--region" && o.cmd == "decode") o.region = next();
         else if (a == "--entropy") {
             const std::string v = next();
             if (v != "device" && v != "zlib" && v != "auto") throw Failure("'" + v + "' isn't a valid value for '--entropy' [values: zlib, device, auto]");
@@ -222,7 +225,27 @@ void decode(const Opts &o)   // src/main.rs:63-71 (always Crossed; metadata.inte
     Grid grid;
     deserialize(read_file(o.input), m, grid);
     hgi::Decoder<Crossed> decoder(Crossed{});
-    save_pgm(decoder.decode({m.width, m.height}, m.scale_level, grid), o.output);
+    if (o.region.empty()) {
+        save_pgm(decoder.decode({m.width, m.height}, m.scale_level, grid), o.output);
+        return;
+    }
+    // --region X,Y,W,H: four unsigned decimal numbers, the window inside the image
+    uint64_t v[4];
+    size_t at = 0;
+    for (int i = 0; i < 4; ++i) {
+        const size_t end = i < 3 ? o.region.find(',', at) : o.region.size();
+        const std::string part = end == std::string::npos ? std::string() : o.region.substr(at, end - at);
+        if (part.empty() || part.size() > 10 || part.find_first_not_of("0123456789") != std::string::npos)
+            throw Failure("--region expects X,Y,W,H (four unsigned integers), got '" + o.region + "'");
+        v[i] = std::stoull(part);
+        at = end + 1;
+    }
+    if (v[2] == 0 || v[3] == 0 || v[0] + v[2] > m.width || v[1] + v[3] > m.height)
+        throw Failure("--region " + o.region + " is empty or does not lie inside the " + std::to_string(m.width) + "x" +
+                      std::to_string(m.height) + " image");
+    save_pgm(decoder.decode_region({m.width, m.height}, m.scale_level, grid, (uint32_t)v[0], (uint32_t)v[1], (uint32_t)v[2],
+                                   (uint32_t)v[3]),
+             o.output);
 }
 
 void test(const Opts &o)   // src/main.rs:73-120

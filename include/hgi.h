@@ -125,6 +125,39 @@ HGI_API hgi_status hgi_decode_u8_dev(hgi_ctx *ctx, const void *d_grid, uint32_t 
                              uint32_t levels, hgi_interp interp, void *d_img, size_t batch,
                              size_t frame_stride);
 
+/* ---- region decode: a window of each frame, at a cost that follows the window ------------------ */
+/* Decode the window [x0, x0 + region_width) x [y0, y0 + region_height) of each of `batch` frames.      */
+/* Output pixel (i, j) of frame f = pixel (x0 + i, y0 + j) of hgi_decode_u8_dev's output, bit for bit.  */
+/* Window row j of frame f goes to d_out + f * out_frame_stride + j * out_pitch, region_width bytes;     */
+/* no other byte of d_out is written.  Async on the ctx stream.                                         */
+/* Only the 128 x 64 tiles of the frame's tile lattice that intersect the window run;   */
+/* pyramids of nine levels and more also decode the frame's stride-256 lattice first (w*h/65536 points) */
+/* in scratch that hgi_ctx_reserve for the FRAME's shape covers; up to eight levels no scratch is used. */
+/* Arguments (HGI_EINVAL unless noted):                                                                 */
+/*  - the window lies inside the frame: x0 + region_width <= width, y0 + region_height <= height,       */
+/*    computed in 64 bits;                                                                              */
+/*  - out_pitch >= region_width; when batch > 1 also frame_stride >= width * height and                 */
+/*    out_frame_stride >= (region_height - 1) * out_pitch + region_width;                               */
+/*  - no aliasing, tested conservatively: the byte interval [d_out, d_out + (batch - 1) *               */
+/*    out_frame_stride + (region_height - 1) * out_pitch + region_width) must not meet [d_grid,         */
+/*    d_grid + (batch - 1) * frame_stride + width * height), even where the frames would interleave;    */
+/*  - a zero-size window, batch == 0, width == 0 or height == 0 succeeds and writes nothing;            */
+/*  - levels, interp and a NULL ctx as for hgi_decode_u8_dev; a ctx set to HGI_PATH_LEVELWISE:          */
+/*    HGI_EUNSUPPORTED (region decode exists on the fused path only).                                   */
+/* Any out_pitch, any alignment of d_out.                                                               */
+HGI_API hgi_status hgi_decode_region_u8_dev(hgi_ctx *ctx, const void *d_grid, uint32_t width, uint32_t height,
+                                            uint32_t levels, hgi_interp interp, uint32_t x0, uint32_t y0,
+                                            uint32_t region_width, uint32_t region_height, void *d_out,
+                                            size_t out_pitch, size_t batch, size_t frame_stride,
+                                            size_t out_frame_stride);
+/* One frame in host memory (pairs with hgi_decode_u8; what the CLI and the Python numpy path call).     */
+/* Synchronous.  The whole grid is uploaded, only the window comes back: window row j goes to           */
+/* out + j * out_pitch.  Same argument rules as above with batch = 1.                                   */
+HGI_API hgi_status hgi_decode_region_u8(hgi_ctx *ctx, const uint8_t *grid, uint32_t width, uint32_t height,
+                                        uint32_t levels, hgi_interp interp, uint32_t x0, uint32_t y0,
+                                        uint32_t region_width, uint32_t region_height, uint8_t *out,
+                                        size_t out_pitch);
+
 /* ---- host-pointer batch calls ------------------------------------------------------------ */
 /* `batch` frames in HOST memory, frame f at base + f * frame_stride (frame_stride >= w*h). */
 /* Synchronous like hgi_encode_u8 / hgi_decode_u8, but the frames are pipelined through the  */

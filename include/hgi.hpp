@@ -171,6 +171,17 @@ class Decoder {
         return image;
     }
 
+    // The window [x0, x0 + w) x [y0, y0 + h) of decode(dimensions, levels, grid), bit for bit, decoded by the tiles that cover
+    // it only (hgi_decode_region_u8).  A window outside the frame throws hgi::Error (HGI_EINVAL).
+    GrayImage decode_region(std::pair<uint32_t, uint32_t> dimensions, size_t levels, const Grid &grid, uint32_t x0, uint32_t y0,
+                            uint32_t w, uint32_t h)
+    {
+        GrayImage image(w, h);
+        check(hgi_decode_region_u8(ctx_.get(), grid.buffer.data(), dimensions.first, dimensions.second,
+                                   static_cast<uint32_t>(levels), I::kernel_id, x0, y0, w, h, image.data.data(), w));
+        return image;
+    }
+
   private:
     I interpolator_;
     Context &ctx_;

@@ -62,6 +62,39 @@ def _check_out(out, like, what):
     return out
 
 
+def _check_rect(rect, width, height, what):
+    """(x0, y0, w, h) of a window that lies inside the (width, height) frame -- checked in Python integers, before any
+    device call (the C ABI takes 32-bit coordinates: x0 = 2**32 - 1 must not wrap into the frame)."""
+    try:
+        x0, y0, w, h = (int(v) for v in rect)
+    except (TypeError, ValueError):
+        raise ValueError("%s: the region is (x0, y0, width, height)" % what)
+    if min(x0, y0, w, h) < 0:
+        raise ValueError("%s: region %r has a negative coordinate or size" % (what, (x0, y0, w, h)))
+    if x0 + w > width or y0 + h > height:
+        raise ValueError("%s: region %r does not lie inside the %dx%d frame" % (what, (x0, y0, w, h), width, height))
+    return x0, y0, w, h
+
+
+def _check_region_out(out, like, shape, what):
+    """`out=` of a region call: a C-contiguous uint8 buffer of the window stack's shape beside `like` (the grids), not
+    overlapping them."""
+    if _is_torch(like):
+        import torch
+        if not _is_torch(out) or out.dtype != torch.uint8 or not out.is_contiguous() or tuple(out.shape) != shape \
+                or out.device != like.device:
+            raise ValueError("%s: `out` must be a contiguous uint8 tensor of shape %s on %s" % (what, shape, like.device))
+        a0, na, b0, nb = like.data_ptr(), like.numel(), out.data_ptr(), out.numel()
+    else:
+        if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags["C_CONTIGUOUS"] \
+                or not out.flags["WRITEABLE"] or out.shape != shape:
+            raise ValueError("%s: `out` must be a writable C-contiguous uint8 array of shape %s" % (what, shape))
+        a0, na, b0, nb = like.ctypes.data, like.size, out.ctypes.data, out.size
+    if a0 < b0 + nb and b0 < a0 + na:
+        raise ValueError("%s: `out` overlaps the input" % what)
+    return out
+
+
 def _np_image(a):
     a = np.ascontiguousarray(a, dtype=np.uint8)
     if a.ndim != 2:
@@ -166,4 +199,51 @@ class Decoder:
         out = torch.empty_like(grids) if out is None else _check_out(out, grids, "decode_batch")
         _ffi.check(_ffi.lib().hgi_decode_u8_dev(ctx.handle, grids.data_ptr(), w, h, int(levels),
                                                 self._interp, out.data_ptr(), b, h * w))
+        return out
+
+    def decode_region(self, dimensions, levels, grid, rect):
+        """The window rect = (x0, y0, w, h) of `decode(dimensions, levels, grid)` as an (h, w) array, bit for bit -- computed by
+        the tiles that cover the window only.  numpy grid: hgi_decode_region_u8 (synchronous); CUDA tensor: a tensor, asynchronous
+        on the current stream (hgi_decode_region_u8_dev)."""
+        width, height = int(dimensions[0]), int(dimensions[1])
+        x0, y0, w, h = _check_rect(rect, width, height, "decode_region")
+        buf = grid.buffer if isinstance(grid, Grid) else grid
+        if _is_torch(buf):
+            if buf.numel() != width * height:
+                raise ValueError("decode_region: the grid holds %d bytes, not %dx%d" % (buf.numel(), width, height))
+            return self.decode_region_batch(buf.reshape(1, height, width), levels, (x0, y0, w, h))[0]
+        g = np.ascontiguousarray(buf, dtype=np.uint8)
+        if g.size != width * height:
+            raise ValueError("decode_region: the grid holds %d bytes, not %dx%d" % (g.size, width, height))
+        g = g.reshape(height, width)
+        img = np.empty((h, w), np.uint8)
+        if w == 0 or h == 0:
+            return img
+        ctx = self._ctx or _ffi.default_context(0)
+        _ffi.check(_ffi.lib().hgi_decode_region_u8(ctx.handle, g.ctypes.data, width, height, int(levels), self._interp,
+                                                   x0, y0, w, h, img.ctypes.data, w))
+        return img
+
+    def decode_region_batch(self, grids, levels, rect, out=None):
+        """(B, H, W) grids -> (B, h, w): the same window of every frame.  CUDA tensor: one hgi_decode_region_u8_dev launch,
+        asynchronous on the current stream; numpy stack: hgi_decode_region_u8 frame by frame.  The window and `out` are
+        validated before any device call."""
+        if grids.ndim != 3:
+            raise ValueError("expected a (batch, height, width) stack")
+        b, height, width = (int(v) for v in grids.shape)
+        x0, y0, w, h = _check_rect(rect, width, height, "decode_region_batch")
+        if not _is_torch(grids):
+            g = np.ascontiguousarray(grids, dtype=np.uint8)
+            out = np.empty((b, h, w), np.uint8) if out is None else _check_region_out(out, g, (b, h, w), "decode_region_batch")
+            for f in range(b):
+                out[f] = self.decode_region((width, height), levels, g[f], (x0, y0, w, h))
+            return out
+        import torch
+        if out is not None:
+            _check_region_out(out, grids, (b, h, w), "decode_region_batch")
+        ctx = _torch_ctx(grids, self._ctx)
+        if out is None:
+            out = torch.empty((b, h, w), dtype=torch.uint8, device=grids.device)
+        _ffi.check(_ffi.lib().hgi_decode_region_u8_dev(ctx.handle, grids.data_ptr(), width, height, int(levels), self._interp,
+                                                       x0, y0, w, h, out.data_ptr(), w, b, height * width, h * w))
         return out

@@ -309,6 +309,77 @@ hgi_status decode_impl(hgi_ctx *c, const uint8_t *grid, uint32_t w, uint32_t h, 
     return HGI_OK;
 }
 
+// The window of every frame, decoded by the tiles of the frame's 128 x 64 lattice that cover it (hgi_fused_region.hip).  Same
+// route per depth as decode_impl (split_pyramid), so the bytes are the full decode's: up to eight levels one launch and no
+// scratch; from nine levels the whole frame's stride-256 lattice first, in decode_impl's planes -- what ws_need covers.
+hgi_status region_impl(hgi_ctx *c, const uint8_t *grid, uint32_t w, uint32_t h, uint32_t levels, int interp, const RegionRect &r,
+                       uint8_t *out, size_t batch, size_t stride)
+{
+    const Frames f = {w, h, (uint64_t)stride, (uint32_t)batch};
+    if (levels == 0) {   // the grid is the image: a strided copy of the window
+        for (size_t b = 0; b < batch; ++b)
+            HIP_TRY(hipMemcpy2DAsync(out + b * r.out_frame_stride, r.out_pitch, grid + b * stride + (size_t)r.y0 * w + r.x0, w, r.width,
+                                     r.height, hipMemcpyDeviceToDevice, c->stream));
+        return HGI_OK;
+    }
+    const Split sp = split_pyramid(levels);
+    if (sp.shift) {
+        const SubGeom g = sub_geom(w, h, sp.shift);
+        uint8_t *sub_grid = ws_take(c, batch * g.stride);
+        uint8_t *sub_rec = ws_take(c, batch * g.stride);
+        if (!sub_grid || !sub_rec) return fail(HGI_ENOMEM, "scratch exhausted (lattice planes)");
+        if (use_lattice_kernel(g, batch)) {
+            HIP_TRY(launch_lattice_pyramid(grid, f, sp.shift, levels - sp.shift, interp, Lut256{}, true, false, nullptr, sub_rec, g.sw,
+                                           g.sh, g.stride, c->stream));
+        } else {
+            HIP_TRY(launch_gather_lattice(grid, f, sp.shift, sub_grid, g.sw, g.sh, g.stride, c->stream));
+            HGI_TRY(decode_impl(c, sub_grid, g.sw, g.sh, levels - sp.shift, interp, sub_rec, batch, g.stride));
+        }
+        const Seeds sd = {sub_rec, nullptr, g.sw, g.sh, g.stride, sp.up};
+        HIP_TRY(launch_decode_region(grid, out, f, r, sp.k, interp, &sd, c->stream));
+    } else if (sp.up) {
+        const Seeds sd = {nullptr, nullptr, 0, 0, 0, sp.up};
+        HIP_TRY(launch_decode_region(grid, out, f, r, sp.k, interp, &sd, c->stream));
+    } else {
+        HIP_TRY(launch_decode_region(grid, out, f, r, sp.k, interp, nullptr, c->stream));
+    }
+    return HGI_OK;
+}
+
+// Arguments of the region calls (include/hgi.h).  HGI_OK with *empty set: nothing to do.
+hgi_status check_region(hgi_ctx *c, const void *grid, uint32_t w, uint32_t h, uint32_t levels, int interp, uint32_t x0, uint32_t y0,
+                        uint32_t rw, uint32_t rh, const void *out, size_t out_pitch, size_t batch, size_t stride, size_t out_stride,
+                        bool *empty)
+{
+    *empty = true;
+    if (!c) return fail(HGI_EINVAL, "ctx is NULL");
+    if (levels > 31) return fail(HGI_EINVAL, "levels %u out of range 0..=31", levels);
+    if (interp != HGI_INTERP_LEFTTOP && interp != HGI_INTERP_CROSSED)
+        return fail(HGI_EUNSUPPORTED, "interpolator %d not implemented (0 = LeftTop, 1 = Crossed)", interp);
+    if (c->path == HGI_PATH_LEVELWISE)
+        return fail(HGI_EUNSUPPORTED, "region decode runs on the fused path only (this ctx is set to HGI_PATH_LEVELWISE)");
+    if (w == 0 || h == 0 || batch == 0) return HGI_OK;
+    if ((uint64_t)x0 + rw > w || (uint64_t)y0 + rh > h)
+        return fail(HGI_EINVAL, "window %u,%u %ux%u does not lie inside the %ux%u frame", x0, y0, rw, rh, w, h);
+    if (rw == 0 || rh == 0) return HGI_OK;
+    if (!grid || !out) return fail(HGI_EINVAL, "NULL buffer");
+    if (out_pitch < rw) return fail(HGI_EINVAL, "out_pitch %zu < region width %u", out_pitch, rw);
+    if (batch > 0x7fffffffu) return fail(HGI_EINVAL, "batch too large");
+    const size_t n = (size_t)w * h;
+    typedef unsigned __int128 u128;
+    const u128 wspan = (u128)(rh - 1) * out_pitch + rw;      // bytes of one frame's window in the output
+    if (batch > 1 && stride < n) return fail(HGI_EINVAL, "frame_stride %zu < width*height", stride);
+    if (batch > 1 && (u128)out_stride < wspan)
+        return fail(HGI_EINVAL, "out_frame_stride %zu < (region_height - 1) * out_pitch + region_width", out_stride);
+    // No aliasing, tested conservatively: the byte interval the output frames span must not meet the one the grid frames span.
+    const u128 pg = reinterpret_cast<uintptr_t>(grid), po = reinterpret_cast<uintptr_t>(out);
+    const u128 ge = pg + (u128)(batch - 1) * (batch > 1 ? stride : 0) + n, oe = po + (u128)(batch - 1) * (batch > 1 ? out_stride : 0) + wspan;
+    if (po < ge && pg < oe) return fail(HGI_EINVAL, "the output span overlaps the grid span: they must not alias");
+    if (wspan + (u128)(batch - 1) * out_stride > (u128)SIZE_MAX) return fail(HGI_EINVAL, "output span too large");
+    *empty = false;
+    return HGI_OK;
+}
+
 hgi_status check_common(hgi_ctx *c, const void *a, const void *b, uint32_t levels, int interp, size_t batch,
                         size_t stride, uint32_t w, uint32_t h)
 {
@@ -809,6 +880,48 @@ hgi_status hgi_decode_u8(hgi_ctx *c, const uint8_t *grid, uint32_t w, uint32_t h
                          hgi_interp interp, uint8_t *img_out)
 {
     return host_roundtrip(c, grid, img_out, w, h, levels, interp, nullptr, false);
+}
+
+hgi_status hgi_decode_region_u8_dev(hgi_ctx *c, const void *d_grid, uint32_t w, uint32_t h, uint32_t levels, hgi_interp interp,
+                                    uint32_t x0, uint32_t y0, uint32_t rw, uint32_t rh, void *d_out, size_t out_pitch, size_t batch,
+                                    size_t frame_stride, size_t out_frame_stride)
+{
+    bool empty;
+    HGI_TRY(check_region(c, d_grid, w, h, levels, interp, x0, y0, rw, rh, d_out, out_pitch, batch, frame_stride, out_frame_stride, &empty));
+    if (empty) return HGI_OK;
+    if (batch == 1 && frame_stride < (size_t)w * h) frame_stride = (size_t)w * h;
+    if (batch == 1) out_frame_stride = 0;
+    HIP_TRY(hipSetDevice(c->device));
+    // the full decode's scratch (none up to eight levels): a ctx reserved for the frame's shape allocates nothing here
+    HGI_TRY(ws_ensure(c, ws_need(c, w, h, levels, batch, frame_stride)));
+    c->ws_used = 0;
+    const RegionRect r = {x0, y0, rw, rh, (uint64_t)out_pitch, (uint64_t)out_frame_stride};
+    return region_impl(c, static_cast<const uint8_t *>(d_grid), w, h, levels, interp, r, static_cast<uint8_t *>(d_out), batch,
+                       frame_stride);
+}
+
+// One frame in host memory: the whole grid goes up into scratch (a tile reads its halo and, deep pyramids, the frame's lattice),
+// only the window comes down.  Sized like host_roundtrip's unbanded staging, so that a ctx reserved for the frame's shape
+// does not grow for it either.
+hgi_status hgi_decode_region_u8(hgi_ctx *c, const uint8_t *grid, uint32_t w, uint32_t h, uint32_t levels, hgi_interp interp, uint32_t x0,
+                                uint32_t y0, uint32_t rw, uint32_t rh, uint8_t *out, size_t out_pitch)
+{
+    bool empty;
+    const size_t n = (size_t)w * h;
+    HGI_TRY(check_region(c, grid, w, h, levels, interp, x0, y0, rw, rh, out, out_pitch, 1, n, 0, &empty));
+    if (empty) return HGI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t slot = align_up(n, 256) + 256;
+    HGI_TRY(ws_ensure(c, 2 * slot + ws_need(c, w, h, levels, 1, n)));
+    c->ws_used = 0;
+    uint8_t *d_in = ws_take(c, n), *d_win = ws_take(c, (size_t)rw * rh);
+    if (!d_in || !d_win) return fail(HGI_ENOMEM, "scratch exhausted (host staging)");
+    HIP_TRY(hipMemcpyAsync(d_in, grid, n, hipMemcpyHostToDevice, c->stream));
+    const RegionRect r = {x0, y0, rw, rh, (uint64_t)rw, 0};
+    HGI_TRY(region_impl(c, d_in, w, h, levels, interp, r, d_win, 1, n));
+    HIP_TRY(hipMemcpy2DAsync(out, out_pitch, d_win, rw, rw, rh, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return HGI_OK;
 }
 
 hgi_status hgi_synth_u8_dev(hgi_ctx *c, hgi_synth_kind kind, uint64_t seed, uint64_t first_frame, uint32_t w,

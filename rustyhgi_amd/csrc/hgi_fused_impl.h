@@ -2013,6 +2013,9 @@ inline u32 xcd_mode(const TileGrid &g, bool encode)
 
 }  // namespace
 
+// The host launchers of the tile builds.  A unit that includes this file for the tile procedure alone and brings a launcher of
+// its own (hgi_fused_region.hip) defines HGI_FUSED_NO_LAUNCHERS: these would be defined twice at link time.
+#ifndef HGI_FUSED_NO_LAUNCHERS
 #ifdef HGI_FUSED_DECODE
 hipError_t HGI_TILED(launch_decode_fused)(const uint8_t *grid, uint8_t *img, const Frames &f, uint32_t k, int interp,
                                           const Seeds *seeds, hipStream_t s, uint32_t row_limit, int resident_tiles)
@@ -2145,5 +2148,6 @@ hipError_t HGI_TILED(launch_encode_fused)(const uint8_t *img, uint8_t *grid, con
 }
 
 #endif  // HGI_FUSED_ENCODE
+#endif  // HGI_FUSED_NO_LAUNCHERS
 
 }  // namespace hgi

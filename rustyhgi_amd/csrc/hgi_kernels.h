@@ -78,6 +78,16 @@ HGI_DECLARE_FUSED(32)
 HGI_DECLARE_FUSED(16)
 #undef HGI_DECLARE_FUSED
 
+// ---- region decode (hgi_fused_region.hip): the tiles of the frame's 128 x 64 lattice that intersect a window -------------
+// Window row j of frame f goes to out + f * out_frame_stride + j * out_pitch (width bytes); nothing else of `out` is written.
+struct RegionRect {
+    uint32_t x0, y0, width, height;
+    uint64_t out_pitch, out_frame_stride;
+};
+// k = fused levels (1 ... kFusedMaxLevels), seeds as for launch_decode_fused_64 (none, or the cone: up >= 1)
+hipError_t launch_decode_region(const uint8_t *grid, uint8_t *out, const Frames &f, const RegionRect &r, uint32_t k, int interp,
+                                const Seeds *seeds, hipStream_t s);
+
 // dst[f][j][i] = src[f][j << k][i << k]  (the stride-2^k lattice as a dense plane)
 hipError_t launch_gather_lattice(const uint8_t *src, const Frames &f, uint32_t k, uint8_t *dst,
                                  uint32_t sw, uint32_t sh, uint64_t dst_stride, hipStream_t s);
