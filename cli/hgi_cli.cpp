@@ -2,8 +2,10 @@
 // MI355X library.  Same subcommands, flags and defaults:
 //
 //   hgi encode -i <input> -o <output> [-l <level>=4] [-q lossless|low|medium|high = medium]
-//   hgi decode -i <input.hgi> -o <output> [--region X,Y,W,H]
-//   (--region: only that window of the image is decoded and written -- no counterpart in the reference)
+//   hgi decode -i <input.hgi> -o <output> [--region X,Y,W,H | --scale N]
+//   (--region: only that window of the image is decoded and written; --scale N, N a power of two from 1 to 2^31: the image at
+//    1 / N resolution, every N-th pixel of every N-th row of the full decode, decoded from the coarse levels alone -- neither has
+//    a counterpart in the reference, and they do not combine)
 //   hgi test <input> [-s <suffix>=""] [-l <level>=4] [-q <quantizator>=medium]
 //   (encode / test also take --entropy zlib|device|auto, default zlib: `device` has the GPU write the archive's DEFLATE stream
 //    as Huffman-coded literals -- same container, readable by the same readers; no counterpart in the reference)
@@ -159,6 +161,7 @@ struct Opts {
     size_t level = 4;                                            // src/options.rs:54
     QuantizationLevel quant = QuantizationLevel::Medium;         // src/options.rs:62
     std::string region;   // --region X,Y,W,H (decode): the window to decode; no reference flag
+    std::string scale;    // --scale N (decode): N a power of two, the image at 1 / N resolution; no reference flag
     int entropy = 0;   // --entropy zlib (0, the reference's writer) | device (1: the GPU's entropy stage) | auto (2: device unless an LZ77 probe says zlib wins); no reference flag
 };
 
@@ -186,6 +189,7 @@ Opts parse(int argc, char **argv)
         else if (a == "-q" || a == "--quantizator") o.quant = parse_level(next());
         else if (a == "-s" || a == "--suffix") o.suffix = next();
         else if (a == "--region" && o.cmd == "decode") o.region = next();
+        else if (a == "--scale" && o.cmd == "decode") o.scale = next();
         else if (a == "--entropy") {
             const std::string v = next();
             if (v != "device" && v != "zlib" && v != "auto") throw Failure("'" + v + "' isn't a valid value for '--entropy' [values: zlib, device, auto]");
@@ -225,6 +229,18 @@ void decode(const Opts &o)   // src/main.rs:63-71 (always Crossed; metadata.inte
     Grid grid;
     deserialize(read_file(o.input), m, grid);
     hgi::Decoder<Crossed> decoder(Crossed{});
+    if (!o.scale.empty()) {
+        if (!o.region.empty()) throw Failure("--scale and --region do not combine: give one of them");
+        // --scale N: an unsigned decimal power of two from 1 to 2^31; shift = log2 N
+        const std::string &t = o.scale;
+        const uint64_t n = t.empty() || t.size() > 10 || t.find_first_not_of("0123456789") != std::string::npos ? 0 : std::stoull(t);
+        if (n == 0 || (n & (n - 1)) != 0 || n > (1ull << 31))
+            throw Failure("--scale expects a power of two from 1 to 2147483648, got '" + t + "'");
+        uint32_t shift = 0;
+        while ((1ull << shift) < n) ++shift;
+        save_pgm(decoder.decode_scaled({m.width, m.height}, m.scale_level, grid, shift), o.output);
+        return;
+    }
     if (o.region.empty()) {
         save_pgm(decoder.decode({m.width, m.height}, m.scale_level, grid), o.output);
         return;

@@ -158,6 +158,33 @@ HGI_API hgi_status hgi_decode_region_u8(hgi_ctx *ctx, const uint8_t *grid, uint3
                                         uint32_t region_width, uint32_t region_height, uint8_t *out,
                                         size_t out_pitch);
 
+/* ---- scaled decode: each frame at 1 / 2^shift resolution, from its coarse levels ------------------- */
+/* Output frame f has sw = ceil(width / 2^shift) columns and sh = ceil(height / 2^shift) rows (computed */
+/* in 64 bits).  Output pixel (i, j) = pixel (i << shift, j << shift) of hgi_decode_u8_dev's output,    */
+/* bit for bit: the coarse levels of the pyramid are exact pixels of the image.  Row j  */
+/* of frame f goes to d_out + f * out_frame_stride + j * out_pitch, sw bytes; no other byte of d_out is */
+/* written.  Async on the ctx stream.  Only the grid bytes of the stride-2^shift lattice are read, and  */
+/* levels - shift levels run on them; shift >= levels is a strided copy of the grid's own lattice.      */
+/* Pyramids with nine levels and more left above the lattice also decode its stride-256 sub-lattice    */
+/* first, in scratch that hgi_ctx_reserve for the FRAME's shape covers; up to eight none is used.       */
+/* Arguments (HGI_EINVAL unless noted):                                                                 */
+/*  - shift <= 31; out_pitch >= sw; when batch > 1 also frame_stride >= width * height and              */
+/*    out_frame_stride >= (sh - 1) * out_pitch + sw;                                                    */
+/*  - no aliasing, tested conservatively on byte spans as for region decode (the output span            */
+/*    (batch - 1) * out_frame_stride + (sh - 1) * out_pitch + sw against the grid span);                */
+/*  - batch == 0, width == 0 or height == 0 succeeds and writes nothing;                                */
+/*  - levels, interp and a NULL ctx as for hgi_decode_u8_dev; a ctx set to HGI_PATH_LEVELWISE:          */
+/*    HGI_EUNSUPPORTED (scaled decode exists on the fused path only).                                   */
+/* Any out_pitch, any alignment of d_out.                                                               */
+HGI_API hgi_status hgi_decode_scaled_u8_dev(hgi_ctx *ctx, const void *d_grid, uint32_t width, uint32_t height,
+                                            uint32_t levels, hgi_interp interp, uint32_t shift, void *d_out,
+                                            size_t out_pitch, size_t batch, size_t frame_stride, size_t out_frame_stride);
+/* One frame in host memory.  Synchronous.  Only the sh grid rows the lattice lies on are uploaded      */
+/* (one 2-D copy), only the sw x sh result comes back: row j goes to out + j * out_pitch.  Same         */
+/* argument rules as above with batch = 1; hgi_ctx_reserve for the frame's shape covers its scratch.    */
+HGI_API hgi_status hgi_decode_scaled_u8(hgi_ctx *ctx, const uint8_t *grid, uint32_t width, uint32_t height,
+                                        uint32_t levels, hgi_interp interp, uint32_t shift, uint8_t *out, size_t out_pitch);
+
 /* ---- host-pointer batch calls ------------------------------------------------------------ */
 /* `batch` frames in HOST memory, frame f at base + f * frame_stride (frame_stride >= w*h). */
 /* Synchronous like hgi_encode_u8 / hgi_decode_u8, but the frames are pipelined through the  */

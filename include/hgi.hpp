@@ -182,6 +182,19 @@ class Decoder {
         return image;
     }
 
+    // decode(dimensions, levels, grid) at 1 / 2^shift resolution: pixel (i, j) is pixel (i << shift, j << shift) of the full
+    // decode, bit for bit, decoded from the coarse levels alone (hgi_decode_scaled_u8).  The image is ceil(width / 2^shift) x
+    // ceil(height / 2^shift).  A shift beyond 31 throws hgi::Error (HGI_EINVAL).
+    GrayImage decode_scaled(std::pair<uint32_t, uint32_t> dimensions, size_t levels, const Grid &grid, uint32_t shift)
+    {
+        const uint32_t sw = shift > 31 ? 0 : (uint32_t)((((uint64_t)dimensions.first + (1ull << shift) - 1) >> shift));
+        const uint32_t sh = shift > 31 ? 0 : (uint32_t)((((uint64_t)dimensions.second + (1ull << shift) - 1) >> shift));
+        GrayImage image(sw, sh);
+        check(hgi_decode_scaled_u8(ctx_.get(), grid.buffer.data(), dimensions.first, dimensions.second, static_cast<uint32_t>(levels),
+                                   I::kernel_id, shift, image.data.data(), sw));
+        return image;
+    }
+
   private:
     I interpolator_;
     Context &ctx_;

@@ -95,6 +95,18 @@ def _check_region_out(out, like, shape, what):
     return out
 
 
+def _check_shift(shift, what):
+    """The scale step: an int from 0 to 31 (bool, float and str are refused, before any device call)."""
+    if isinstance(shift, (bool, np.bool_)) or not isinstance(shift, (int, np.integer)) or not 0 <= int(shift) <= 31:
+        raise ValueError("%s: shift must be an int from 0 to 31, not %r" % (what, shift))
+    return int(shift)
+
+
+def scaled_size(width, height, shift):
+    """(sw, sh) = (ceil(width / 2**shift), ceil(height / 2**shift)): the frame of a scaled decode."""
+    return -(-int(width) >> int(shift)), -(-int(height) >> int(shift))
+
+
 def _np_image(a):
     a = np.ascontiguousarray(a, dtype=np.uint8)
     if a.ndim != 2:
@@ -246,4 +258,55 @@ class Decoder:
             out = torch.empty((b, h, w), dtype=torch.uint8, device=grids.device)
         _ffi.check(_ffi.lib().hgi_decode_region_u8_dev(ctx.handle, grids.data_ptr(), width, height, int(levels), self._interp,
                                                        x0, y0, w, h, out.data_ptr(), w, b, height * width, h * w))
+        return out
+
+    def decode_scaled(self, dimensions, levels, grid, shift):
+        """`decode(dimensions, levels, grid)[::2**shift, ::2**shift]` as an (sh, sw) array, bit for bit -- decoded from the grid
+        bytes of that lattice with levels - shift levels.  numpy grid: hgi_decode_scaled_u8 (synchronous, uploads only the rows
+        it reads); CUDA tensor: a tensor, asynchronous on the current stream (hgi_decode_scaled_u8_dev)."""
+        shift = _check_shift(shift, "decode_scaled")
+        width, height = int(dimensions[0]), int(dimensions[1])
+        sw, sh = scaled_size(width, height, shift)
+        buf = grid.buffer if isinstance(grid, Grid) else grid
+        if _is_torch(buf):
+            if buf.numel() != width * height:
+                raise ValueError("decode_scaled: the grid holds %d bytes, not %dx%d" % (buf.numel(), width, height))
+            return self.decode_scaled_batch(buf.reshape(1, height, width), levels, shift)[0]
+        g = np.ascontiguousarray(buf, dtype=np.uint8)
+        if g.size != width * height:
+            raise ValueError("decode_scaled: the grid holds %d bytes, not %dx%d" % (g.size, width, height))
+        g = g.reshape(height, width)
+        img = np.empty((sh, sw), np.uint8)
+        if width == 0 or height == 0:
+            return img
+        ctx = self._ctx or _ffi.default_context(0)
+        _ffi.check(_ffi.lib().hgi_decode_scaled_u8(ctx.handle, g.ctypes.data, width, height, int(levels), self._interp, shift,
+                                                   img.ctypes.data, sw))
+        return img
+
+    def decode_scaled_batch(self, grids, levels, shift, out=None):
+        """(B, H, W) grids -> (B, sh, sw): every frame at 1 / 2**shift resolution.  CUDA tensor: one hgi_decode_scaled_u8_dev
+        call, asynchronous on the current stream; numpy stack: hgi_decode_scaled_u8 frame by frame.  `shift` and `out` are
+        validated before any device call."""
+        shift = _check_shift(shift, "decode_scaled_batch")
+        if grids.ndim != 3:
+            raise ValueError("expected a (batch, height, width) stack")
+        b, height, width = (int(v) for v in grids.shape)
+        sw, sh = scaled_size(width, height, shift)
+        if not _is_torch(grids):
+            g = np.ascontiguousarray(grids, dtype=np.uint8)
+            out = np.empty((b, sh, sw), np.uint8) if out is None else _check_region_out(out, g, (b, sh, sw), "decode_scaled_batch")
+            for f in range(b):
+                out[f] = self.decode_scaled((width, height), levels, g[f], shift)
+            return out
+        import torch
+        if out is not None:
+            _check_region_out(out, grids, (b, sh, sw), "decode_scaled_batch")
+        ctx = _torch_ctx(grids, self._ctx)
+        if out is None:
+            out = torch.empty((b, sh, sw), dtype=torch.uint8, device=grids.device)
+        if b == 0 or width == 0 or height == 0:
+            return out
+        _ffi.check(_ffi.lib().hgi_decode_scaled_u8_dev(ctx.handle, grids.data_ptr(), width, height, int(levels), self._interp,
+                                                       shift, out.data_ptr(), sw, b, height * width, sh * sw))
         return out

@@ -380,6 +380,77 @@ hgi_status check_region(hgi_ctx *c, const void *grid, uint32_t w, uint32_t h, ui
     return HGI_OK;
 }
 
+// The stride-2^shift lattice of every frame (hgi_fused_scaled.hip).  `rp`: source bytes between the view's rows -- w << shift on
+// the device, w on the host call's compact plane of the rows it uploaded; `bytes`: the bytes of one source frame.  The view is an
+// sw x sh image with levels - shift levels, routed per depth as decode_impl routes a frame: up to eight levels
+// one launch and no scratch; deeper, the view's stride-256 lattice is gathered and decoded first.
+hgi_status scaled_impl(hgi_ctx *c, const uint8_t *grid, uint32_t w, uint32_t h, uint64_t rp, uint64_t bytes, uint32_t levels, int interp,
+                       uint32_t shift, uint8_t *out, size_t out_pitch, size_t batch, size_t stride, size_t out_stride)
+{
+    const uint32_t sw = (uint32_t)((((uint64_t)w - 1) >> shift) + 1), sh = (uint32_t)((((uint64_t)h - 1) >> shift) + 1);
+    if (shift == 0) {   // the whole decode into the pitched output
+        const RegionRect r = {0, 0, w, h, (uint64_t)out_pitch, (uint64_t)out_stride};
+        return region_impl(c, grid, w, h, levels, interp, r, out, batch, stride);
+    }
+    if (shift >= levels) {   // every point of the lattice is a grid byte that no pass touches: a pitched strided gather
+        HIP_TRY(launch_gather_view(grid, stride, rp, 0, shift, sw, sh, out, out_pitch, out_stride, (uint32_t)batch, c->stream));
+        return HGI_OK;
+    }
+    const uint32_t lv = levels - shift;
+    const ScaledView v = {sw, sh, shift, rp, bytes, (uint64_t)stride, (uint32_t)batch, (uint64_t)out_pitch, (uint64_t)out_stride};
+    const Split sp = split_pyramid(lv);
+    if (sp.shift) {
+        const SubGeom g = sub_geom(sw, sh, sp.shift);
+        uint8_t *sub_grid = ws_take(c, batch * g.stride);
+        uint8_t *sub_rec = ws_take(c, batch * g.stride);
+        if (!sub_grid || !sub_rec) return fail(HGI_ENOMEM, "scratch exhausted (lattice planes)");
+        // the view's stride-2^sp.shift lattice = the grid's stride-2^(shift + sp.shift) lattice: an HGI image of its own
+        HIP_TRY(launch_gather_view(grid, stride, rp, sp.shift, shift + sp.shift, g.sw, g.sh, sub_grid, g.sw, g.stride, (uint32_t)batch,
+                                   c->stream));
+        HGI_TRY(decode_impl(c, sub_grid, g.sw, g.sh, lv - sp.shift, interp, sub_rec, batch, g.stride));
+        const Seeds sd = {sub_rec, nullptr, g.sw, g.sh, g.stride, sp.up};
+        HIP_TRY(launch_decode_scaled(grid, out, v, sp.k, interp, &sd, c->stream));
+    } else if (sp.up) {
+        const Seeds sd = {nullptr, nullptr, 0, 0, 0, sp.up};
+        HIP_TRY(launch_decode_scaled(grid, out, v, sp.k, interp, &sd, c->stream));
+    } else {
+        HIP_TRY(launch_decode_scaled(grid, out, v, sp.k, interp, nullptr, c->stream));
+    }
+    return HGI_OK;
+}
+
+// Arguments of the scaled calls (include/hgi.h): check_region's rules with the window replaced by sw x sh.  HGI_OK with *empty
+// set: nothing to do.
+hgi_status check_scaled(hgi_ctx *c, const void *grid, uint32_t w, uint32_t h, uint32_t levels, int interp, uint32_t shift, const void *out,
+                        size_t out_pitch, size_t batch, size_t stride, size_t out_stride, bool *empty)
+{
+    *empty = true;
+    if (!c) return fail(HGI_EINVAL, "ctx is NULL");
+    if (levels > 31) return fail(HGI_EINVAL, "levels %u out of range 0..=31", levels);
+    if (interp != HGI_INTERP_LEFTTOP && interp != HGI_INTERP_CROSSED)
+        return fail(HGI_EUNSUPPORTED, "interpolator %d not implemented (0 = LeftTop, 1 = Crossed)", interp);
+    if (shift > 31) return fail(HGI_EINVAL, "shift %u out of range 0..=31", shift);
+    if (c->path == HGI_PATH_LEVELWISE)
+        return fail(HGI_EUNSUPPORTED, "scaled decode runs on the fused path only (this ctx is set to HGI_PATH_LEVELWISE)");
+    if (w == 0 || h == 0 || batch == 0) return HGI_OK;
+    const uint64_t sw = (((uint64_t)w - 1) >> shift) + 1, sh = (((uint64_t)h - 1) >> shift) + 1;
+    if (!grid || !out) return fail(HGI_EINVAL, "NULL buffer");
+    if (out_pitch < sw) return fail(HGI_EINVAL, "out_pitch %zu < scaled width %llu", out_pitch, (unsigned long long)sw);
+    if (batch > 0x7fffffffu) return fail(HGI_EINVAL, "batch too large");
+    const size_t n = (size_t)w * h;
+    typedef unsigned __int128 u128;
+    const u128 span = (u128)(sh - 1) * out_pitch + sw;      // bytes of one output frame
+    if (batch > 1 && stride < n) return fail(HGI_EINVAL, "frame_stride %zu < width*height", stride);
+    if (batch > 1 && (u128)out_stride < span)
+        return fail(HGI_EINVAL, "out_frame_stride %zu < (scaled_height - 1) * out_pitch + scaled_width", out_stride);
+    const u128 pg = reinterpret_cast<uintptr_t>(grid), po = reinterpret_cast<uintptr_t>(out);
+    const u128 ge = pg + (u128)(batch - 1) * (batch > 1 ? stride : 0) + n, oe = po + (u128)(batch - 1) * (batch > 1 ? out_stride : 0) + span;
+    if (po < ge && pg < oe) return fail(HGI_EINVAL, "the output span overlaps the grid span: they must not alias");
+    if (span + (u128)(batch - 1) * out_stride > (u128)SIZE_MAX) return fail(HGI_EINVAL, "output span too large");
+    *empty = false;
+    return HGI_OK;
+}
+
 hgi_status check_common(hgi_ctx *c, const void *a, const void *b, uint32_t levels, int interp, size_t batch,
                         size_t stride, uint32_t w, uint32_t h)
 {
@@ -920,6 +991,48 @@ hgi_status hgi_decode_region_u8(hgi_ctx *c, const uint8_t *grid, uint32_t w, uin
     const RegionRect r = {x0, y0, rw, rh, (uint64_t)rw, 0};
     HGI_TRY(region_impl(c, d_in, w, h, levels, interp, r, d_win, 1, n));
     HIP_TRY(hipMemcpy2DAsync(out, out_pitch, d_win, rw, rw, rh, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return HGI_OK;
+}
+
+hgi_status hgi_decode_scaled_u8_dev(hgi_ctx *c, const void *d_grid, uint32_t w, uint32_t h, uint32_t levels, hgi_interp interp,
+                                    uint32_t shift, void *d_out, size_t out_pitch, size_t batch, size_t frame_stride, size_t out_frame_stride)
+{
+    bool empty;
+    HGI_TRY(check_scaled(c, d_grid, w, h, levels, interp, shift, d_out, out_pitch, batch, frame_stride, out_frame_stride, &empty));
+    if (empty) return HGI_OK;
+    const size_t n = (size_t)w * h;
+    if (batch == 1 && frame_stride < n) frame_stride = n;
+    if (batch == 1) out_frame_stride = 0;
+    HIP_TRY(hipSetDevice(c->device));
+    // at most the full decode's scratch (none up to eight levels above the lattice): a ctx reserved for the frame's shape
+    // allocates nothing here
+    HGI_TRY(ws_ensure(c, ws_need(c, w, h, levels, batch, frame_stride)));
+    c->ws_used = 0;
+    return scaled_impl(c, static_cast<const uint8_t *>(d_grid), w, h, (uint64_t)w << shift, n, levels, interp, shift,
+                       static_cast<uint8_t *>(d_out), out_pitch, batch, frame_stride, out_frame_stride);
+}
+
+// One frame in host memory: only the sh grid rows the lattice lies on go up (one 2-D copy into a compact w x sh plane, the view's
+// row pitch is then w), only the sw x sh result comes down.  Sized by host_call_need, the formula hgi_ctx_reserve uses: the two
+// staging slots hold at most a frame each, the lattice planes are at most the full decode's.
+hgi_status hgi_decode_scaled_u8(hgi_ctx *c, const uint8_t *grid, uint32_t w, uint32_t h, uint32_t levels, hgi_interp interp, uint32_t shift,
+                                uint8_t *out, size_t out_pitch)
+{
+    bool empty;
+    const size_t n = (size_t)w * h;
+    HGI_TRY(check_scaled(c, grid, w, h, levels, interp, shift, out, out_pitch, 1, n, 0, &empty));
+    if (empty) return HGI_OK;
+    const uint32_t sw = (uint32_t)((((uint64_t)w - 1) >> shift) + 1), sh = (uint32_t)((((uint64_t)h - 1) >> shift) + 1);
+    HIP_TRY(hipSetDevice(c->device));
+    HGI_TRY(ws_ensure(c, host_call_need(c, w, h, levels)));
+    c->ws_used = 0;
+    const size_t cn = (size_t)w * sh;
+    uint8_t *d_in = ws_take(c, cn), *d_out = ws_take(c, (size_t)sw * sh);
+    if (!d_in || !d_out) return fail(HGI_ENOMEM, "scratch exhausted (host staging)");
+    HIP_TRY(hipMemcpy2DAsync(d_in, w, grid, (size_t)w << shift, w, sh, hipMemcpyHostToDevice, c->stream));
+    HGI_TRY(scaled_impl(c, d_in, w, h, (uint64_t)w, cn, levels, interp, shift, d_out, sw, 1, cn, 0));
+    HIP_TRY(hipMemcpy2DAsync(out, out_pitch, d_out, sw, sw, sh, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return HGI_OK;
 }

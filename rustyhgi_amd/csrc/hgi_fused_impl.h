@@ -1437,10 +1437,16 @@ __device__ __forceinline__ u32 cone_corner(u32 x, u32 y, u32 A, u32 B, u32 T, u3
     return (((y & ~m2) - (B & ~m2)) >> (T + 1)) * nx2 + (((x & ~m2) - (A & ~m2)) >> (T + 1));
 }
 
+// Where byte (x, y) of a W-wide frame lives, relative to the frame's first byte: the frame's own row-major layout.  (Scaled decode,
+// hgi_fused_scaled.hip, brings a view of its own: every 2^s-th byte of every row it reads.)
+struct FrameAt {
+    __device__ __forceinline__ size_t operator()(size_t x, size_t y, u32 W) const { return y * W + x; }
+};
+
 // Index work and the one load; nothing here waits.  fr: the frame (source or grid).  Pyramids deeper than 4 + sd.up levels: the
 // base points come from the seed planes (stride-2^(4 + up) lattice, coded by earlier launches) instead of the frame.
-template <bool WANT_Q>
-__device__ __forceinline__ ConeLane cone_issue(const u8 *__restrict__ fr, u32 W, u32 H, const Seeds &sd, Tile tl)
+template <bool WANT_Q, class At = FrameAt>
+__device__ __forceinline__ ConeLane cone_issue(const u8 *__restrict__ fr, u32 W, u32 H, const Seeds &sd, Tile tl, At at = At{})
 {
     const u32 up = sd.up, sw = ((W - 1u) >> 4) + 1u, sh = ((H - 1u) >> 4) + 1u;      // the stride-16 plane
     constexpr u32 o2 = cone_off(2), o3 = cone_off(3), o4 = cone_off(4), o5 = cone_off(5);
@@ -1473,7 +1479,7 @@ __device__ __forceinline__ ConeLane cone_issue(const u8 *__restrict__ fr, u32 W,
             if (WANT_Q) c.vq = sd.q[at];
         }
     } else if (c.in1 && !framed) {
-        c.v = fr[((size_t)y << 4) * W + ((size_t)x << 4)];
+        c.v = fr[at((size_t)x << 4, (size_t)y << 4, W)];
     }
     if (!WANT_Q || !sd.rec) c.vq = c.v;      // base samples of the frame itself: residual == sample
     // level 0: the seeds

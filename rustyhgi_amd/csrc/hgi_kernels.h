@@ -88,6 +88,23 @@ struct RegionRect {
 hipError_t launch_decode_region(const uint8_t *grid, uint8_t *out, const Frames &f, const RegionRect &r, uint32_t k, int interp,
                                 const Seeds *seeds, hipStream_t s);
 
+// ---- scaled decode (hgi_fused_scaled.hip): the stride-2^shift lattice of every frame, from the grid bytes of that lattice -----
+// The source is a VIEW: a width x height frame whose byte (x, y) is src[f * frame_stride + y * row_pitch + (x << shift)], and
+// whose rows below `height` read as 0 (frame_bytes: the bytes of one source frame, all of them inside the caller's buffer).
+// Output row j of frame f goes to out + f * out_frame_stride + j * out_pitch (width bytes); nothing else of `out` is written.
+struct ScaledView {
+    uint32_t width, height, shift;
+    uint64_t row_pitch, frame_bytes, frame_stride;
+    uint32_t batch;
+    uint64_t out_pitch, out_frame_stride;
+};
+// k = fused levels of the view's pyramid (1 ... kFusedMaxLevels), seeds as for launch_decode_region (none, or the cone)
+hipError_t launch_decode_scaled(const uint8_t *src, uint8_t *out, const ScaledView &v, uint32_t k, int interp, const Seeds *seeds,
+                                hipStream_t s);
+// dst[f][y * dst_pitch + x] = src[f * src_stride + (y << ky) * row_pitch + (x << kx)], x < sw, y < sh
+hipError_t launch_gather_view(const uint8_t *src, uint64_t src_stride, uint64_t row_pitch, uint32_t ky, uint32_t kx, uint32_t sw,
+                              uint32_t sh, uint8_t *dst, uint64_t dst_pitch, uint64_t dst_stride, uint32_t batch, hipStream_t s);
+
 // dst[f][j][i] = src[f][j << k][i << k]  (the stride-2^k lattice as a dense plane)
 hipError_t launch_gather_lattice(const uint8_t *src, const Frames &f, uint32_t k, uint8_t *dst,
                                  uint32_t sw, uint32_t sh, uint64_t dst_stride, hipStream_t s);
