@@ -94,7 +94,8 @@ HGI_API hgi_status hgi_ctx_set_path(hgi_ctx *ctx, hgi_path path);
 HGI_API hgi_status hgi_ctx_reserve(hgi_ctx *ctx, uint32_t width, uint32_t height, uint32_t levels,
                            size_t batch);
 /* Bytes of device scratch the ctx owns right now (0 after hgi_ctx_create): memory accounting,  */
-/* and the way to see that a reserved ctx does not re-allocate.                                */
+/* and the way to see that a reserved ctx does not re-allocate.  Includes the frame lists'      */
+/* descriptor tables and their pinned staging (hgi_*_u8_list_dev).                              */
 HGI_API hgi_status hgi_ctx_scratch_bytes(hgi_ctx *ctx, size_t *bytes);
 HGI_API hgi_status hgi_sync(hgi_ctx *ctx);
 HGI_API const char *hgi_last_error(void);
@@ -184,6 +185,34 @@ HGI_API hgi_status hgi_decode_scaled_u8_dev(hgi_ctx *ctx, const void *d_grid, ui
 /* argument rules as above with batch = 1; hgi_ctx_reserve for the frame's shape covers its scratch.    */
 HGI_API hgi_status hgi_decode_scaled_u8(hgi_ctx *ctx, const uint8_t *grid, uint32_t width, uint32_t height,
                                         uint32_t levels, hgi_interp interp, uint32_t shift, uint8_t *out, size_t out_pitch);
+
+/* ---- frame lists: frames of different shapes in one call ------------------------------------------ */
+/* Frame i is widths[i] x heights[i], tightly packed at d_imgs[i] / d_grids[i] (device pointers, any      */
+/* alignment); its output is bit for bit what hgi_encode_u8_dev / hgi_decode_u8_dev write for that frame  */
+/* alone.  Levels, interpolator and table are shared by the list (group by them in the caller).           */
+/* The pointer and size arrays are HOST memory, read before the call returns: the caller may reuse or     */
+/* free them at once.  `lut` as for hgi_encode_u8_dev.  Async on the ctx stream.                          */
+/* Levels 1 ... 8 run as ONE launch over the 128 x 64 tiles of every frame; levels 0 and  */
+/* from nine on are served frame by frame through the uniform calls (batch 1): correct, not batched.      */
+/* The per-frame table goes up through a ring of ctx-owned slots (pinned staging + device table, both     */
+/* grow-only, counted by hgi_ctx_scratch_bytes, freed by hgi_ctx_destroy); a call waits only for the      */
+/* launch that last read the slot it reuses.  The scratch block is never touched by levels 1 ... 8.       */
+/* Arguments (HGI_EINVAL unless noted):                                                                   */
+/*  - count == 0 succeeds and does nothing; frames with width or height 0 are skipped (their pointers     */
+/*    are not used);                                                                                      */
+/*  - a NULL array with count > 0, or a NULL frame pointer of a non-empty frame, is refused;              */
+/*  - overlaps, on byte spans [p, p + width * height): the outputs must be pairwise disjoint and no       */
+/*    output may meet any input; inputs may overlap each other (one grid may be listed twice);            */
+/*  - more tiles than one launch holds (2^31 - 16) is refused;                                            */
+/*  - levels, interp and a NULL ctx as for hgi_decode_u8_dev; a ctx set to HGI_PATH_LEVELWISE, and a ctx  */
+/*    stream that is being captured into a graph: HGI_EUNSUPPORTED (a replay would read a table that      */
+/*    later calls overwrite).                                                                             */
+HGI_API hgi_status hgi_encode_u8_list_dev(hgi_ctx *ctx, const void *const *d_imgs, const uint32_t *widths,
+                                          const uint32_t *heights, uint32_t levels, hgi_interp interp,
+                                          const uint8_t lut[256], void *const *d_grids, size_t count);
+HGI_API hgi_status hgi_decode_u8_list_dev(hgi_ctx *ctx, const void *const *d_grids, const uint32_t *widths,
+                                          const uint32_t *heights, uint32_t levels, hgi_interp interp,
+                                          void *const *d_imgs, size_t count);
 
 /* ---- host-pointer batch calls ------------------------------------------------------------ */
 /* `batch` frames in HOST memory, frame f at base + f * frame_stride (frame_stride >= w*h). */

@@ -107,6 +107,97 @@ def scaled_size(width, height, shift):
     return -(-int(width) >> int(shift)), -(-int(height) >> int(shift))
 
 
+def _spans_meet(spans):
+    """spans: (lo, hi, is_output) byte ranges.  True when two outputs meet or an output meets an input (inputs may overlap each
+    other) -- include/hgi.h's rule for frame lists, by one sorted sweep."""
+    hi_any = hi_out = 0
+    for lo, hi, is_out in sorted(s for s in spans if s[1] > s[0]):
+        if lo < hi_out or (is_out and lo < hi_any):
+            return True
+        hi_any = max(hi_any, hi)
+        if is_out:
+            hi_out = max(hi_out, hi)
+    return False
+
+
+def _check_list(frames, out, what):
+    """A frame list -- 2-D uint8 arrays, all torch CUDA tensors on one device (contiguous) or all numpy arrays -- and its `out=`
+    list: the same shapes, uint8, C-contiguous, beside the inputs, no output meeting another output or any input.  Everything is
+    decided here, before any device call.  Returns (frames, is_torch)."""
+    if not isinstance(frames, (list, tuple)):
+        raise ValueError("%s: expected a list of (height, width) frames" % what)
+    frames = list(frames)
+    torch_in = [_is_torch(f) for f in frames]
+    if any(torch_in) and not all(torch_in):
+        raise ValueError("%s: the list mixes torch tensors and other arrays" % what)
+    use_torch = bool(frames) and all(torch_in)
+    if use_torch:
+        import torch
+        dev = frames[0].device
+        for i, f in enumerate(frames):
+            if f.dtype != torch.uint8 or f.dim() != 2 or not f.is_contiguous():
+                raise ValueError("%s: frame %d must be a contiguous (height, width) uint8 tensor" % (what, i))
+            if f.device != dev:
+                raise ValueError("%s: frame %d lives on %s, frame 0 on %s: one device per list" % (what, i, f.device, dev))
+            if max(f.shape) >= 2 ** 32:
+                raise ValueError("%s: frame %d is too large" % (what, i))
+        spans = [(f.data_ptr(), f.data_ptr() + f.numel(), False) for f in frames]
+    else:
+        for i, f in enumerate(frames):
+            if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 2:
+                raise ValueError("%s: frame %d must be a (height, width) uint8 array" % (what, i))
+        frames = [np.ascontiguousarray(f) for f in frames]
+        spans = [(f.ctypes.data, f.ctypes.data + f.size, False) for f in frames]
+    if use_torch and frames[0].device.type != "cuda":
+        on_host = "torch tensors must live on the GPU (use numpy for host buffers)"
+    else:
+        on_host = None
+    if out is None:
+        if on_host:
+            raise ValueError(on_host)
+        return frames, use_torch
+    if not isinstance(out, (list, tuple)) or len(out) != len(frames):
+        raise ValueError("%s: `out` must be a list of %d frames" % (what, len(frames)))
+    for i, (f, o) in enumerate(zip(frames, out)):
+        if use_torch:
+            import torch
+            ok = _is_torch(o) and o.dtype == torch.uint8 and o.is_contiguous() and o.shape == f.shape and o.device == f.device
+            lo = o.data_ptr() if ok else 0
+        else:
+            ok = isinstance(o, np.ndarray) and o.dtype == np.uint8 and o.flags["C_CONTIGUOUS"] and o.flags["WRITEABLE"] \
+                and o.shape == f.shape
+            lo = o.ctypes.data if ok else 0
+        if not ok:
+            raise ValueError("%s: `out` frame %d must be a C-contiguous uint8 buffer of shape %s beside the input"
+                             % (what, i, tuple(f.shape)))
+        spans.append((lo, lo + int(np.prod(f.shape)), True))
+    if _spans_meet(spans):
+        raise ValueError("%s: `out` frames overlap each other or the input" % what)
+    if on_host:
+        raise ValueError(on_host)
+    return frames, use_torch
+
+
+def _list_out(frames):
+    """Outputs of a torch frame list: (h, w) views into ONE allocation, each frame at a 256-B offset."""
+    import torch
+    offs, total = [], 0
+    for f in frames:
+        offs.append(total)
+        total += (f.numel() + 255) // 256 * 256
+    buf = torch.empty((total,), dtype=torch.uint8, device=frames[0].device)
+    return [buf[o:o + f.numel()].view(f.shape) for o, f in zip(offs, frames)]
+
+
+def _list_arrays(frames, outs):
+    """The C ABI's host arrays of a list call: input pointers, widths, heights, output pointers."""
+    n = len(frames)
+    ptrs = ctypes.c_void_p * n
+    u32s = ctypes.c_uint32 * n
+    return (ptrs(*[f.data_ptr() for f in frames]), u32s(*[int(f.shape[1]) for f in frames]),
+            u32s(*[int(f.shape[0]) for f in frames]), ptrs(*[o.data_ptr() for o in outs]))
+
+
 def _np_image(a):
     a = np.ascontiguousarray(a, dtype=np.uint8)
     if a.ndim != 2:
@@ -166,6 +257,27 @@ class Encoder:
                                                 self._interp, self._lut.ctypes.data,
                                                 out.data_ptr(), b, h * w))
         return out
+
+    def encode_list(self, images, out=None):
+        """A list of (h_i, w_i) uint8 frames of any shapes -> the list of their residual planes.  CUDA tensors (one device,
+        contiguous): ONE hgi_encode_u8_list_dev call, asynchronous on the current stream, the outputs (h_i, w_i) views into one
+        allocation unless `out` (a list of tensors) is given.  numpy arrays: hgi_encode_u8 frame by frame.  The list and `out`
+        are validated before any device call."""
+        frames, use_torch = _check_list(images, out, "encode_list")
+        if not use_torch:
+            outs = [np.empty_like(f) for f in frames] if out is None else list(out)
+            ctx = self._ctx or _ffi.default_context(0) if any(f.size for f in frames) else None
+            for f, o in zip(frames, outs):
+                if f.size:
+                    _ffi.check(_ffi.lib().hgi_encode_u8(ctx.handle, f.ctypes.data, f.shape[1], f.shape[0], self.scale_level,
+                                                        self._interp, self._lut.ctypes.data, o.ctypes.data))
+            return outs
+        ctx = _torch_ctx(frames[0], self._ctx)
+        outs = _list_out(frames) if out is None else list(out)
+        ins, ws, hs, ptrs = _list_arrays(frames, outs)
+        _ffi.check(_ffi.lib().hgi_encode_u8_list_dev(ctx.handle, ins, ws, hs, self.scale_level, self._interp,
+                                                     self._lut.ctypes.data, ptrs, len(frames)))
+        return outs
 
 
 class Decoder:
@@ -310,3 +422,22 @@ class Decoder:
         _ffi.check(_ffi.lib().hgi_decode_scaled_u8_dev(ctx.handle, grids.data_ptr(), width, height, int(levels), self._interp,
                                                        shift, out.data_ptr(), sw, b, height * width, sh * sw))
         return out
+
+    def decode_list(self, grids, levels, out=None):
+        """A list of (h_i, w_i) uint8 grids of any shapes, all coded with `levels` -> the list of their images.  CUDA tensors:
+        ONE hgi_decode_u8_list_dev call, asynchronous on the current stream (outputs as in Encoder.encode_list); numpy arrays:
+        hgi_decode_u8 frame by frame.  The list and `out` are validated before any device call."""
+        frames, use_torch = _check_list(grids, out, "decode_list")
+        if not use_torch:
+            outs = [np.empty_like(f) for f in frames] if out is None else list(out)
+            ctx = self._ctx or _ffi.default_context(0) if any(f.size for f in frames) else None
+            for f, o in zip(frames, outs):
+                if f.size:
+                    _ffi.check(_ffi.lib().hgi_decode_u8(ctx.handle, f.ctypes.data, f.shape[1], f.shape[0], int(levels),
+                                                        self._interp, o.ctypes.data))
+            return outs
+        ctx = _torch_ctx(frames[0], self._ctx)
+        outs = _list_out(frames) if out is None else list(out)
+        ins, ws, hs, ptrs = _list_arrays(frames, outs)
+        _ffi.check(_ffi.lib().hgi_decode_u8_list_dev(ctx.handle, ins, ws, hs, int(levels), self._interp, ptrs, len(frames)))
+        return outs

@@ -10,6 +10,7 @@
 #include <thread>
 #include <vector>
 
+#include "hgi_framelist.h"
 #include "hgi_host.h"
 
 using namespace hgi;
@@ -451,6 +452,123 @@ hgi_status check_scaled(hgi_ctx *c, const void *grid, uint32_t w, uint32_t h, ui
     return HGI_OK;
 }
 
+// ---- frame lists (hgi_encode_u8_list_dev / hgi_decode_u8_list_dev) --------------------------------------
+// Arguments of a list call (include/hgi.h), everything decided before any device work.  HGI_OK with *empty set: nothing to do.
+hgi_status check_list(hgi_ctx *c, const void *const *in, const uint32_t *w, const uint32_t *h, uint32_t levels, int interp,
+                      void *const *out, size_t count, bool *empty)
+{
+    *empty = true;
+    if (!c) return fail(HGI_EINVAL, "ctx is NULL");
+    if (levels > 31) return fail(HGI_EINVAL, "levels %u out of range 0..=31", levels);
+    if (interp != HGI_INTERP_LEFTTOP && interp != HGI_INTERP_CROSSED)
+        return fail(HGI_EUNSUPPORTED, "interpolator %d not implemented (0 = LeftTop, 1 = Crossed)", interp);
+    if (c->path == HGI_PATH_LEVELWISE)
+        return fail(HGI_EUNSUPPORTED, "frame lists run on the fused path only (this ctx is set to HGI_PATH_LEVELWISE)");
+    if (count == 0) return HGI_OK;
+    if (!in || !w || !h || !out) return fail(HGI_EINVAL, "NULL array");
+    // A capture would record a launch that reads a descriptor table the ctx's next list call overwrites.
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const hipError_t ce = hipStreamIsCapturing(c->stream, &cs);
+    if (ce != hipSuccess) (void)hipGetLastError();
+    if (ce != hipSuccess || cs != hipStreamCaptureStatusNone)
+        return fail(HGI_EUNSUPPORTED, "frame lists cannot be captured into a graph (the ctx stream is capturing)");
+    std::vector<ListSpan> spans;
+    spans.reserve(2 * count);
+    uint64_t tiles = 0;
+    for (size_t i = 0; i < count; ++i) {
+        if (w[i] == 0 || h[i] == 0) continue;
+        if (!in[i] || !out[i]) return fail(HGI_EINVAL, "frame %zu: NULL buffer", i);
+        const uint64_t n = (uint64_t)w[i] * h[i], pi = reinterpret_cast<uintptr_t>(in[i]), po = reinterpret_cast<uintptr_t>(out[i]);
+        if (pi + n < pi || po + n < po) return fail(HGI_EINVAL, "frame %zu: the buffer wraps the address space", i);
+        spans.push_back({pi, pi + n, i, false});
+        spans.push_back({po, po + n, i, true});
+        tiles += list_tiles(w[i], h[i]);
+    }
+    if (spans.empty()) return HGI_OK;
+    size_t a = 0, b = 0;
+    const int ov = list_overlap(spans, &a, &b);
+    if (ov == 1) return fail(HGI_EINVAL, "the outputs of frames %zu and %zu overlap", a, b);
+    if (ov == 2) return fail(HGI_EINVAL, "the output of frame %zu overlaps the input of frame %zu: they must not alias", a, b);
+    if (list_blocks(tiles, 0) + 8 >= (1ull << 31))
+        return fail(HGI_EINVAL, "the list has %llu tiles: more than one launch holds", (unsigned long long)tiles);
+    *empty = false;
+    return HGI_OK;
+}
+
+hgi_status list_events_ensure(hgi_ctx *c)
+{
+    if (c->have_list_events) return HGI_OK;
+    for (int i = 0; i < hgi_ctx::kListSlots; ++i)
+        if (hipEventCreateWithFlags(&c->ev_list[i], hipEventDisableTiming) != hipSuccess)
+            return fail(HGI_EDEVICE, "event creation failed");   // (a partial set is reclaimed with the process)
+    c->have_list_events = true;
+    return HGI_OK;
+}
+
+// The next slot of the ring, holding at least `bytes`: waits for the launch that last read it (long done unless the caller
+// queues more list calls than there are slots), grows it if it must.  Never touches the scratch block.
+hgi_status list_slot(hgi_ctx *c, size_t bytes, int *slot)
+{
+    HGI_TRY(list_events_ensure(c));
+    const int i = c->list_next;
+    c->list_next = (i + 1) % hgi_ctx::kListSlots;
+    if (c->list_live[i]) {
+        HIP_TRY(hipEventSynchronize(c->ev_list[i]));
+        c->list_live[i] = false;
+    }
+    if (bytes > c->list_bytes[i]) {
+        if (c->list_pin[i]) HIP_TRY(hipHostFree(c->list_pin[i]));
+        if (c->list_dev[i]) HIP_TRY(hipFree(c->list_dev[i]));
+        c->list_pin[i] = c->list_dev[i] = nullptr;
+        c->list_bytes[i] = 0;
+        const size_t grown = align_up(bytes < 4096 ? 4096 : bytes + bytes / 2, 4096);
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->list_pin[i]), grown, hipHostMallocDefault));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->list_dev[i]), grown));
+        c->list_bytes[i] = grown;
+    }
+    *slot = i;
+    return HGI_OK;
+}
+
+// One launch per call for levels 1 ... 8 (the routes of split_pyramid that need no lattice planes); the caller has checked the
+// arguments.  src / dst: the frames' input and output.
+hgi_status list_impl(hgi_ctx *c, const void *const *src, const uint32_t *w, const uint32_t *h, uint32_t levels, int interp,
+                     const uint8_t *lut, void *const *dst, size_t count)
+{
+    size_t m = 0;
+    uint32_t max_w = 0;
+    for (size_t i = 0; i < count; ++i)
+        if (w[i] && h[i]) ++m, max_w = w[i] > max_w ? w[i] : max_w;
+    const size_t tbl = align_up(m * sizeof(ListFrame), 256), pre = align_up(m * sizeof(uint32_t), 256);
+    int slot;
+    HGI_TRY(list_slot(c, tbl + 2 * pre, &slot));
+    uint8_t *pin = c->list_pin[slot], *dev = c->list_dev[slot];
+    static_assert(sizeof(void *) == sizeof(uint64_t), "64-bit device addresses");
+    ListArgs a;
+    uint32_t ne = 0, ni = 0;
+    a.count = plan_list(reinterpret_cast<const uint64_t *>(src), reinterpret_cast<const uint64_t *>(dst), w, h, count,
+                        HGI_SWITCH(HGI_FORCE_CHECKED), reinterpret_cast<ListFrame *>(pin), reinterpret_cast<uint32_t *>(pin + tbl),
+                        reinterpret_cast<uint32_t *>(pin + tbl + pre), &ne, &ni);
+    a.nedge = ne;
+    a.nint = ni;
+    a.frames = reinterpret_cast<const ListFrame *>(dev);
+    a.epre = reinterpret_cast<const uint32_t *>(dev + tbl);
+    a.ipre = reinterpret_cast<const uint32_t *>(dev + tbl + pre);
+    HIP_TRY(hipMemcpyAsync(dev, pin, tbl + 2 * pre, hipMemcpyHostToDevice, c->stream));
+    const Split sp = split_pyramid(levels);
+    const Seeds cone = {nullptr, nullptr, 0, 0, 0, sp.up};
+    hipError_t e;
+    if (lut)
+        e = launch_encode_list(a, sp.k, interp, pack_lut(lut), is_identity(lut), sp.up ? &cone : nullptr, c->stream);
+    else
+        e = launch_decode_list(a, max_w, sp.k, interp, sp.up ? &cone : nullptr, c->stream);
+    // the slot is in use from the copy on, whether or not the launch went out
+    HIP_TRY(hipEventRecord(c->ev_list[slot], c->stream));
+    c->list_live[slot] = true;
+    HIP_TRY(e);
+    return HGI_OK;
+}
+
 hgi_status check_common(hgi_ctx *c, const void *a, const void *b, uint32_t levels, int interp, size_t batch,
                         size_t stride, uint32_t w, uint32_t h)
 {
@@ -588,6 +706,12 @@ void hgi_ctx_destroy(hgi_ctx *c)
     (void)hipStreamSynchronize(c->stream);
     if (c->ws) (void)hipFree(c->ws);
     if (c->pin) (void)hipHostFree(c->pin);
+    for (int i = 0; i < hgi_ctx::kListSlots; ++i) {
+        if (c->list_live[i]) (void)hipEventSynchronize(c->ev_list[i]);   // (a list launch on a stream the ctx no longer uses)
+        if (c->list_pin[i]) (void)hipHostFree(c->list_pin[i]);
+        if (c->list_dev[i]) (void)hipFree(c->list_dev[i]);
+        if (c->have_list_events) (void)hipEventDestroy(c->ev_list[i]);
+    }
     (void)hipEventDestroy(c->ev0);
     (void)hipEventDestroy(c->ev1);
     for (int i = 0; i < 2; ++i) {
@@ -648,6 +772,7 @@ hgi_status hgi_ctx_scratch_bytes(hgi_ctx *c, size_t *bytes)
 {
     if (!c || !bytes) return fail(HGI_EINVAL, "NULL argument");
     *bytes = c->ws_bytes;
+    for (int i = 0; i < hgi_ctx::kListSlots; ++i) *bytes += 2 * c->list_bytes[i];   // the frame lists' tables and their staging
     return HGI_OK;
 }
 
@@ -1035,6 +1160,41 @@ hgi_status hgi_decode_scaled_u8(hgi_ctx *c, const uint8_t *grid, uint32_t w, uin
     HIP_TRY(hipMemcpy2DAsync(out, out_pitch, d_out, sw, sw, sh, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return HGI_OK;
+}
+
+// Frame lists: levels 1 ... 8 in one launch over the tiles of every frame (hgi_fused_list_*.hip); levels 0 and from nine on
+// frame by frame through the uniform calls (a deep pyramid's lattice planes are per-frame scratch).
+hgi_status hgi_encode_u8_list_dev(hgi_ctx *c, const void *const *d_imgs, const uint32_t *widths, const uint32_t *heights, uint32_t levels,
+                                  hgi_interp interp, const uint8_t lut[256], void *const *d_grids, size_t count)
+{
+    bool empty;
+    HGI_TRY(check_list(c, d_imgs, widths, heights, levels, interp, d_grids, count, &empty));
+    if (!lut) return fail(HGI_EINVAL, "lut is NULL");
+    if (empty) return HGI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (levels == 0 || levels > 8) {
+        for (size_t i = 0; i < count; ++i)
+            if (widths[i] && heights[i])
+                HGI_TRY(hgi_encode_u8_dev(c, d_imgs[i], widths[i], heights[i], levels, interp, lut, d_grids[i], 1, (size_t)widths[i] * heights[i]));
+        return HGI_OK;
+    }
+    return list_impl(c, d_imgs, widths, heights, levels, interp, lut, d_grids, count);
+}
+
+hgi_status hgi_decode_u8_list_dev(hgi_ctx *c, const void *const *d_grids, const uint32_t *widths, const uint32_t *heights, uint32_t levels,
+                                  hgi_interp interp, void *const *d_imgs, size_t count)
+{
+    bool empty;
+    HGI_TRY(check_list(c, d_grids, widths, heights, levels, interp, d_imgs, count, &empty));
+    if (empty) return HGI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (levels == 0 || levels > 8) {
+        for (size_t i = 0; i < count; ++i)
+            if (widths[i] && heights[i])
+                HGI_TRY(hgi_decode_u8_dev(c, d_grids[i], widths[i], heights[i], levels, interp, d_imgs[i], 1, (size_t)widths[i] * heights[i]));
+        return HGI_OK;
+    }
+    return list_impl(c, d_grids, widths, heights, levels, interp, nullptr, d_imgs, count);
 }
 
 hgi_status hgi_synth_u8_dev(hgi_ctx *c, hgi_synth_kind kind, uint64_t seed, uint64_t first_frame, uint32_t w,

@@ -31,6 +31,16 @@ struct hgi_ctx {
     size_t pin_bytes;
     int probe_resident_tiles; // -1 except inside the placement probe, whose decode launches run at a fixed occupancy (hgi_planes.hip)
     char planes_report[384];  // what the last hgi_planes_alloc on this ctx found and did (hgi_planes_report)
+    // frame lists (hgi_*_u8_list_dev): a ring of descriptor-table slots, each a pinned staging area and a device table of
+    // list_bytes[i] bytes (grow-only, freed by hgi_ctx_destroy).  ev_list[i] is recorded behind the launch that reads slot i; a
+    // later call waits for it before it writes the slot again, on whichever stream that launch went to.
+    static constexpr int kListSlots = 4;
+    uint8_t *list_pin[kListSlots], *list_dev[kListSlots];
+    size_t list_bytes[kListSlots];
+    hipEvent_t ev_list[kListSlots];
+    bool list_live[kListSlots];   // ev_list[i] has been recorded
+    bool have_list_events;
+    int list_next;
 };
 
 namespace hgi {

@@ -105,6 +105,15 @@ hipError_t launch_decode_scaled(const uint8_t *src, uint8_t *out, const ScaledVi
 hipError_t launch_gather_view(const uint8_t *src, uint64_t src_stride, uint64_t row_pitch, uint32_t ky, uint32_t kx, uint32_t sw,
                               uint32_t sh, uint8_t *dst, uint64_t dst_pitch, uint64_t dst_stride, uint32_t batch, hipStream_t s);
 
+// ---- frame lists (hgi_fused_list_dec.hip / hgi_fused_list_enc.hip): the 128 x 64 tiles of many frames of different shapes
+// in one launch.  ListArgs (hgi_framelist.h): the device table of the frames and the prefix arrays the blocks search.
+// k = fused levels (1 ... kFusedMaxLevels); seeds: none, or the cone on the frame's own samples (k == 4, rec == nullptr).
+// max_width: the widest frame (the decoder's occupancy policy).
+struct ListArgs;
+hipError_t launch_decode_list(const ListArgs &a, uint32_t max_width, uint32_t k, int interp, const Seeds *seeds, hipStream_t s);
+hipError_t launch_encode_list(const ListArgs &a, uint32_t k, int interp, const Lut256 &lut, bool ident, const Seeds *seeds,
+                              hipStream_t s);
+
 // dst[f][j][i] = src[f][j << k][i << k]  (the stride-2^k lattice as a dense plane)
 hipError_t launch_gather_lattice(const uint8_t *src, const Frames &f, uint32_t k, uint8_t *dst,
                                  uint32_t sw, uint32_t sh, uint64_t dst_stride, hipStream_t s);
