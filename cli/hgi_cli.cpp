@@ -1,7 +1,9 @@
 // hgi -- C++ counterpart of the reference CLI (src/main.rs:41-134, src/options.rs:13-65) on the
 // MI355X library.  Same subcommands, flags and defaults:
 //
-//   hgi encode -i <input> -o <output> [-l <level>=4] [-q lossless|low|medium|high = medium]
+//   hgi encode -i <input> -o <output> [-l <level>=4] [-q lossless|low|medium|high = medium] [--crop X,Y,W,H]
+//   (--crop: only that window of the input image is encoded -- one pitched call on the loaded image, no copy of the window; the
+//    archive's metadata carries the window's size -- no counterpart in the reference)
 //   hgi decode -i <input.hgi> -o <output> [--region X,Y,W,H | --scale N]
 //   (--region: only that window of the image is decoded and written; --scale N, N a power of two from 1 to 2^31: the image at
 //    1 / N resolution, every N-th pixel of every N-th row of the full decode, decoded from the coarse levels alone -- neither has
@@ -161,6 +163,7 @@ struct Opts {
     size_t level = 4;                                            // src/options.rs:54
     QuantizationLevel quant = QuantizationLevel::Medium;         // src/options.rs:62
     std::string region;   // --region X,Y,W,H (decode): the window to decode; no reference flag
+    std::string crop;     // --crop X,Y,W,H (encode): the window of the input to encode; no reference flag
     std::string scale;    // --scale N (decode): N a power of two, the image at 1 / N resolution; no reference flag
     int entropy = 0;   // --entropy zlib (0, the reference's writer) | device (1: the GPU's entropy stage) | auto (2: device unless an LZ77 probe says zlib wins); no reference flag
 };
@@ -190,6 +193,7 @@ Opts parse(int argc, char **argv)
         else if (a == "-s" || a == "--suffix") o.suffix = next();
         else if (a == "--region" && o.cmd == "decode") o.region = next();
         else if (a == "--scale" && o.cmd == "decode") o.scale = next();
+        else if (a == "--crop" && o.cmd == "encode") o.crop = next();
         else if (a == "--entropy") {
             const std::string v = next();
             if (v != "device" && v != "zlib" && v != "auto") throw Failure("'" + v + "' isn't a valid value for '--entropy' [values: zlib, device, auto]");
@@ -209,6 +213,23 @@ std::string file_stem(const std::string &path)
     return dot == std::string::npos || dot == 0 ? name : name.substr(0, dot);
 }
 
+// --region / --crop X,Y,W,H: four unsigned decimal numbers, a non-empty window inside the width x height image
+void parse_window(const std::string &flag, const std::string &text, uint32_t width, uint32_t height, uint64_t v[4])
+{
+    size_t at = 0;
+    for (int i = 0; i < 4; ++i) {
+        const size_t end = i < 3 ? text.find(',', at) : text.size();
+        const std::string part = end == std::string::npos ? std::string() : text.substr(at, end - at);
+        if (part.empty() || part.size() > 10 || part.find_first_not_of("0123456789") != std::string::npos)
+            throw Failure(flag + " expects X,Y,W,H (four unsigned integers), got '" + text + "'");
+        v[i] = std::stoull(part);
+        at = end + 1;
+    }
+    if (v[2] == 0 || v[3] == 0 || v[0] + v[2] > width || v[1] + v[3] > height)
+        throw Failure(flag + " " + text + " is empty or does not lie inside the " + std::to_string(width) + "x" + std::to_string(height) +
+                      " image");
+}
+
 // ---- subcommands -------------------------------------------------------------------------------------
 void encode(const Opts &o)   // src/main.rs:41-61
 {
@@ -216,8 +237,17 @@ void encode(const Opts &o)   // src/main.rs:41-61
     GrayImage image = open_image(o.input);
     Linear quantizator = Linear::from(o.quant);
     hgi::Encoder<Crossed, Linear> encoder(Crossed{}, quantizator, o.level);
-    const uint32_t width = image.width, height = image.height;
-    Grid grid = encoder.encode(std::move(image));
+    uint32_t width = image.width, height = image.height;
+    Grid grid;
+    if (!o.crop.empty()) {   // the window where it lies in the loaded image: its first pixel, the image's width as row pitch
+        uint64_t v[4];
+        parse_window("--crop", o.crop, width, height, v);
+        grid = encoder.encode_view(image.data.data() + v[1] * width + v[0], width, (uint32_t)v[2], (uint32_t)v[3]);
+        width = (uint32_t)v[2];
+        height = (uint32_t)v[3];
+    } else {
+        grid = encoder.encode(std::move(image));
+    }
     Metadata metadata{o.quant, InterpolationType::Crossed, width, height, o.level};
     write_file(o.output, write_archive(o, metadata, grid));
 }
@@ -245,20 +275,8 @@ void decode(const Opts &o)   // src/main.rs:63-71 (always Crossed; metadata.inte
         save_pgm(decoder.decode({m.width, m.height}, m.scale_level, grid), o.output);
         return;
     }
-    // --region X,Y,W,H: four unsigned decimal numbers, the window inside the image
     uint64_t v[4];
-    size_t at = 0;
-    for (int i = 0; i < 4; ++i) {
-        const size_t end = i < 3 ? o.region.find(',', at) : o.region.size();
-        const std::string part = end == std::string::npos ? std::string() : o.region.substr(at, end - at);
-        if (part.empty() || part.size() > 10 || part.find_first_not_of("0123456789") != std::string::npos)
-            throw Failure("--region expects X,Y,W,H (four unsigned integers), got '" + o.region + "'");
-        v[i] = std::stoull(part);
-        at = end + 1;
-    }
-    if (v[2] == 0 || v[3] == 0 || v[0] + v[2] > m.width || v[1] + v[3] > m.height)
-        throw Failure("--region " + o.region + " is empty or does not lie inside the " + std::to_string(m.width) + "x" +
-                      std::to_string(m.height) + " image");
+    parse_window("--region", o.region, m.width, m.height, v);
     save_pgm(decoder.decode_region({m.width, m.height}, m.scale_level, grid, (uint32_t)v[0], (uint32_t)v[1], (uint32_t)v[2],
                                    (uint32_t)v[3]),
              o.output);

@@ -13,7 +13,10 @@
  *    thread-local message of the last failure;
  *  - images and grids are tightly packed row-major u8, stride == width
  *    (reference: GrayImage / Grid, src/grid.rs:2-27); a batch is `batch`
- *    frames `frame_stride` bytes apart;
+ *    frames `frame_stride` bytes apart.  The *_pitched calls alone take rows
+ *    `pitch` >= width bytes apart, with a pitch and a frame stride of its own
+ *    for the input and for the output (crops, canvas windows, padded planes);
+ *    the region and scaled calls give their OUTPUT a pitch;
  *  - there is NO CPU fallback in this library: without a usable HIP device
  *    hgi_ctx_create fails with HGI_EDEVICE;
  *  - a ctx is not thread-safe; distinct ctxs are independent;
@@ -185,6 +188,56 @@ HGI_API hgi_status hgi_decode_scaled_u8_dev(hgi_ctx *ctx, const void *d_grid, ui
 /* argument rules as above with batch = 1; hgi_ctx_reserve for the frame's shape covers its scratch.    */
 HGI_API hgi_status hgi_decode_scaled_u8(hgi_ctx *ctx, const uint8_t *grid, uint32_t width, uint32_t height,
                                         uint32_t levels, hgi_interp interp, uint32_t shift, uint8_t *out, size_t out_pitch);
+
+/* ---- pitched frames: rows `pitch` >= width bytes apart, a pitch of its own on each side ------------- */
+/* A crop of a larger device image (d_img = parent + y0 * parent_width + x0, img_pitch = parent_width), a */
+/* window of a canvas as decode target, planes with padded rows (hipMallocPitch, video surfaces): coded   */
+/* where they lie, without a packing copy.  Row y of frame f lies at base + f * frame_stride + y * pitch,  */
+/* `width` bytes.  Output frame f, read through its pitch, is bit for bit what hgi_encode_u8_dev /          */
+/* hgi_decode_u8_dev write for the packed copy of input frame f.  Async on the ctx stream.                 */
+/*  - ONLY the `width` bytes of each output row are written: the bytes between rows (pitch - width),       */
+/*    between frames and around the span keep their values -- they may be a parent image's live pixels.    */
+/*  - Reads stay inside each input frame's span [p, p + (height - 1) * pitch + width), plus at most three  */
+/*    bytes behind the last frame's span when width is not a multiple of 4 and those bytes lie in the      */
+/*    same 4-KiB page as the span's last byte (otherwise a byte-checked path runs).  Gap bytes inside the  */
+/*    span may be read; their values never influence the result -- they are foreign data, not zeros, and   */
+/*    corners beyond width / height read 0 whatever the gap holds.                                         */
+/*  - Any pitch >= width, any alignment of base, pitch and frame stride; the two pitches are independent.  */
+/*    Rows run on 16-B accesses whatever the width: a 1918-wide frame at pitch 2048 on a 128-B aligned     */
+/*    base has every row start on a line boundary, which its packed form cannot have.      */
+/*  - When both pitches equal `width` (and, batch > 1, both frame strides are one number) the call         */
+/*    forwards to hgi_encode_u8_dev / hgi_decode_u8_dev: same kernels, tile order and tile heights.        */
+/*    Otherwise 128 x 64 tiles in a simple walk (ragged tiles first, then row-major per frame).            */
+/*  - Scratch: what hgi_ctx_reserve(width, height, levels, batch) covers; none up to eight levels.  From   */
+/*    nine levels the stride-256 lattice is gathered through the pitch and coded in scratch first.         */
+/*    Graph capture: as for the uniform _dev calls (reserve first; no table, no per-call device state).    */
+/* Arguments (HGI_EINVAL unless noted):                                                                    */
+/*  - a pitch < width; when batch > 1 a frame stride < (height - 1) * pitch + width of its side;           */
+/*  - no aliasing, tested conservatively on byte spans as for region decode: [d_in, d_in + (batch - 1) *   */
+/*    in_frame_stride + in_span) must not meet the output's interval -- two windows interleaved in one     */
+/*    parent allocation (side by side in the same rows) are refused; windows of different allocations, or  */
+/*    one above the other, are fine;                                                                       */
+/*  - batch == 0, width == 0 or height == 0 succeeds and writes nothing;                                   */
+/*  - levels, interp, lut and a NULL ctx as for the uniform calls; a ctx set to HGI_PATH_LEVELWISE:        */
+/*    HGI_EUNSUPPORTED (pitched frames exist on the fused path only).                                      */
+HGI_API hgi_status hgi_encode_u8_pitched_dev(hgi_ctx *ctx, const void *d_img, size_t img_pitch, uint32_t width,
+                                             uint32_t height, uint32_t levels, hgi_interp interp,
+                                             const uint8_t lut[256], void *d_grid, size_t grid_pitch, size_t batch,
+                                             size_t img_frame_stride, size_t grid_frame_stride);
+HGI_API hgi_status hgi_decode_u8_pitched_dev(hgi_ctx *ctx, const void *d_grid, size_t grid_pitch, uint32_t width,
+                                             uint32_t height, uint32_t levels, hgi_interp interp, void *d_img,
+                                             size_t img_pitch, size_t batch, size_t grid_frame_stride,
+                                             size_t img_frame_stride);
+/* One frame in host memory.  Synchronous.  Upload and download are 2-D copies of the width-byte rows     */
+/* only (the gaps are neither read nor written); between them the packed frame runs the uniform route --  */
+/* the host calls are transfer-bound.  Same argument rules as above with batch = 1; hgi_ctx_reserve for   */
+/* the frame's shape covers the scratch.                                                                  */
+HGI_API hgi_status hgi_encode_u8_pitched(hgi_ctx *ctx, const uint8_t *img, size_t img_pitch, uint32_t width,
+                                         uint32_t height, uint32_t levels, hgi_interp interp,
+                                         const uint8_t lut[256], uint8_t *grid_out, size_t grid_pitch);
+HGI_API hgi_status hgi_decode_u8_pitched(hgi_ctx *ctx, const uint8_t *grid, size_t grid_pitch, uint32_t width,
+                                         uint32_t height, uint32_t levels, hgi_interp interp, uint8_t *img_out,
+                                         size_t img_pitch);
 
 /* ---- frame lists: frames of different shapes in one call ------------------------------------------ */
 /* Frame i is widths[i] x heights[i], tightly packed at d_imgs[i] / d_grids[i] (device pointers, any      */

@@ -148,6 +148,17 @@ class Encoder {
         return grid;
     }
 
+    // A VIEW: `width` x `height` pixels whose rows lie `pitch` >= width bytes apart -- a crop of a larger image (pointer to its
+    // first pixel, the parent's width as pitch), a plane with padded rows -- encoded where it lies (hgi_encode_u8_pitched: only the
+    // width bytes of each row are read).  Bit for bit encode() of the packed copy.  A pitch below the width throws hgi::Error.
+    Grid encode_view(const uint8_t *pixels, size_t pitch, uint32_t width, uint32_t height)
+    {
+        Grid grid(width, height);
+        check(hgi_encode_u8_pitched(ctx_.get(), pixels, pitch, width, height, static_cast<uint32_t>(scale_level_), I::kernel_id,
+                                    table_.data(), grid.buffer.data(), width));
+        return grid;
+    }
+
   private:
     I interpolator_;
     Q quantizator_;
@@ -193,6 +204,14 @@ class Decoder {
         check(hgi_decode_scaled_u8(ctx_.get(), grid.buffer.data(), dimensions.first, dimensions.second, static_cast<uint32_t>(levels),
                                    I::kernel_id, shift, image.data.data(), sw));
         return image;
+    }
+
+    // decode(dimensions, levels, grid) written into a VIEW: row y goes to out + y * pitch, `width` bytes -- a window of a canvas,
+    // say; no other byte of `out` is written (hgi_decode_u8_pitched).  A pitch below the width throws hgi::Error.
+    void decode_view(std::pair<uint32_t, uint32_t> dimensions, size_t levels, const Grid &grid, uint8_t *out, size_t pitch)
+    {
+        check(hgi_decode_u8_pitched(ctx_.get(), grid.buffer.data(), dimensions.first, dimensions.first, dimensions.second,
+                                    static_cast<uint32_t>(levels), I::kernel_id, out, pitch));
     }
 
   private:

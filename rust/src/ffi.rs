@@ -28,6 +28,14 @@ extern "C" {
                              frame_stride: usize) -> c_int;
     pub fn hgi_decode_u8_dev(ctx: *mut HgiCtx, d_grid: *const c_void, width: u32, height: u32, levels: u32,
                              interp: c_int, d_img: *mut c_void, batch: usize, frame_stride: usize) -> c_int;
+    /// include/hgi.h: frames whose rows lie `pitch` >= width bytes apart (a crop of a larger device image, a window of a canvas),
+    /// a pitch and a frame stride of its own on each side; only the width bytes of each output row are written
+    pub fn hgi_encode_u8_pitched_dev(ctx: *mut HgiCtx, d_img: *const c_void, img_pitch: usize, width: u32, height: u32, levels: u32,
+                                     interp: c_int, lut: *const u8, d_grid: *mut c_void, grid_pitch: usize, batch: usize,
+                                     img_frame_stride: usize, grid_frame_stride: usize) -> c_int;
+    pub fn hgi_decode_u8_pitched_dev(ctx: *mut HgiCtx, d_grid: *const c_void, grid_pitch: usize, width: u32, height: u32, levels: u32,
+                                     interp: c_int, d_img: *mut c_void, img_pitch: usize, batch: usize, grid_frame_stride: usize,
+                                     img_frame_stride: usize) -> c_int;
     pub fn hgi_sync(ctx: *mut HgiCtx) -> c_int;
     /// include/hgi.h: raw DEFLATE of a grid's bincode image, entropy-coded on the device (grid in host memory)
     pub fn hgi_deflate_grid(ctx: *mut HgiCtx, grid: *const u8, width: u32, height: u32, out: *mut u8, cap: usize,

@@ -41,6 +41,10 @@ SYMBOLS = [
     ("hgi_decode_region_u8", _int, [_vp, _vp, _u32, _u32, _u32, _int, _u32, _u32, _u32, _u32, _vp, _sz]),
     ("hgi_decode_scaled_u8_dev", _int, [_vp, _vp, _u32, _u32, _u32, _int, _u32, _vp, _sz, _sz, _sz, _sz]),
     ("hgi_decode_scaled_u8", _int, [_vp, _vp, _u32, _u32, _u32, _int, _u32, _vp, _sz]),
+    ("hgi_encode_u8_pitched_dev", _int, [_vp, _vp, _sz, _u32, _u32, _u32, _int, _vp, _vp, _sz, _sz, _sz, _sz]),
+    ("hgi_decode_u8_pitched_dev", _int, [_vp, _vp, _sz, _u32, _u32, _u32, _int, _vp, _sz, _sz, _sz, _sz]),
+    ("hgi_encode_u8_pitched", _int, [_vp, _vp, _sz, _u32, _u32, _u32, _int, _vp, _vp, _sz]),
+    ("hgi_decode_u8_pitched", _int, [_vp, _vp, _sz, _u32, _u32, _u32, _int, _vp, _sz]),
     ("hgi_encode_u8_list_dev", _int, [_vp, _vp, _vp, _vp, _u32, _int, _vp, _vp, _sz]),
     ("hgi_decode_u8_list_dev", _int, [_vp, _vp, _vp, _vp, _u32, _int, _vp, _sz]),
     ("hgi_synth_u8_dev", _int, [_vp, _int, _u64, _u64, _u32, _u32, _vp, _sz, _sz]),

@@ -34,6 +34,12 @@ def _torch_ctx(t, ctx=None):
         raise ValueError("torch tensors must live on the GPU (use numpy for host buffers)")
     if t.dtype != torch.uint8 or not t.is_contiguous():
         raise ValueError("expected a contiguous uint8 tensor")
+    return _bind_ctx(t, ctx)
+
+
+def _bind_ctx(t, ctx=None):
+    """The context of CUDA tensor `t`'s device, bound to torch's current stream there."""
+    import torch
     dev = t.device.index if t.device.index is not None else torch.cuda.current_device()
     if ctx is None:
         ctx = _ffi.default_context(dev)
@@ -198,6 +204,75 @@ def _list_arrays(frames, outs):
             u32s(*[int(f.shape[0]) for f in frames]), ptrs(*[o.data_ptr() for o in outs]))
 
 
+def _view_layout(x, what):
+    """The layout of a pitched view: a 2-D (height, width) or 3-D (batch, height, width) uint8 torch tensor or numpy array whose
+    last dimension has stride 1, whose rows lie >= width bytes apart and whose frames lie uniformly >= one frame's span apart --
+    any slice t[f0:f1, y0:y1, x0:x1] of a contiguous buffer.  Returns (ptr, batch, height, width, pitch, frame_stride, span) in
+    bytes, span = (height - 1) * pitch + width.  Everything else -- other strides (steps, negative steps, expanded dimensions),
+    dtypes, ranks -- raises ValueError; nothing here touches a device."""
+    if _is_torch(x):
+        import torch
+        if x.dtype != torch.uint8:
+            raise ValueError("%s: expected a uint8 tensor, not %s" % (what, x.dtype))
+        shape, strides = tuple(int(v) for v in x.shape), tuple(int(v) for v in x.stride())
+    elif isinstance(x, np.ndarray):
+        if x.dtype != np.uint8:
+            raise ValueError("%s: expected a uint8 array, not %s" % (what, x.dtype))
+        shape, strides = tuple(int(v) for v in x.shape), tuple(int(v) for v in x.strides)
+    else:
+        raise ValueError("%s: expected a uint8 torch CUDA tensor or numpy array" % what)
+    if len(shape) not in (2, 3):
+        raise ValueError("%s: expected a (height, width) or (batch, height, width) view, not %d dimensions" % (what, len(shape)))
+    if len(shape) == 2:
+        shape, strides = (1,) + shape, (0,) + strides
+    (b, h, w), (sf, sr, sc) = shape, strides
+    if max(shape) >= 2 ** 32:
+        raise ValueError("%s: the view is too large" % what)
+    ptr = (x.data_ptr() if _is_torch(x) else x.ctypes.data) if b * h * w else 0
+    if b * h * w == 0:
+        return ptr, b, h, w, w, h * w, h * w
+    if w > 1 and sc != 1:
+        raise ValueError("%s: the last dimension must have stride 1, not %d" % (what, sc))
+    if h > 1 and sr < w:
+        raise ValueError("%s: the row stride %d is smaller than the width %d" % (what, sr, w))
+    pitch = sr if h > 1 else w
+    span = (h - 1) * pitch + w
+    if b > 1 and sf < span:
+        raise ValueError("%s: the frame stride %d is smaller than a frame's span %d" % (what, sf, span))
+    return ptr, b, h, w, pitch, (sf if b > 1 else span), span
+
+
+def _view_out(out, like, lay, what):
+    """`out=` of a view call: None (a packed buffer of the input's shape is allocated beside it) or a view of the input's kind,
+    shape and device whose byte span does not meet the input's.  Returns (out, its layout)."""
+    if out is None:
+        if _is_torch(like):
+            import torch
+            out = torch.empty(tuple(like.shape), dtype=torch.uint8, device=like.device)
+        else:
+            out = np.empty(like.shape, np.uint8)
+        return out, _view_layout(out, what)
+    if _is_torch(like) != _is_torch(out):
+        raise ValueError("%s: `out` must be a %s like the input" % (what, "torch tensor" if _is_torch(like) else "numpy array"))
+    olay = _view_layout(out, what + " (out)")
+    if tuple(out.shape) != tuple(like.shape):
+        raise ValueError("%s: `out` has shape %s, the input %s" % (what, tuple(out.shape), tuple(like.shape)))
+    if _is_torch(like):
+        if out.device != like.device:
+            raise ValueError("%s: `out` lives on %s, the input on %s" % (what, out.device, like.device))
+    elif not out.flags["WRITEABLE"]:
+        raise ValueError("%s: `out` is not writable" % what)
+    (a0, ab, _, _, _, afs, aspan), (b0, bb, _, _, _, bfs, bspan) = lay, olay
+    if ab and a0 < b0 + (bb - 1) * bfs + bspan and b0 < a0 + (ab - 1) * afs + aspan:
+        raise ValueError("%s: `out` shares memory with the input (byte spans, tested conservatively)" % what)
+    return out, olay
+
+
+def _view_device(x, what):
+    if _is_torch(x) and not x.is_cuda:
+        raise ValueError("%s: torch tensors must live on the GPU (use numpy for host buffers)" % what)
+
+
 def _np_image(a):
     a = np.ascontiguousarray(a, dtype=np.uint8)
     if a.ndim != 2:
@@ -256,6 +331,32 @@ class Encoder:
         _ffi.check(_ffi.lib().hgi_encode_u8_dev(ctx.handle, images.data_ptr(), w, h, self.scale_level,
                                                 self._interp, self._lut.ctypes.data,
                                                 out.data_ptr(), b, h * w))
+        return out
+
+    def encode_view(self, images, out=None):
+        """Encode a VIEW: a (H, W) or (B, H, W) uint8 slice t[f0:f1, y0:y1, x0:x1] of a larger buffer -- last dimension stride 1,
+        any row stride >= W, a uniform frame stride -- where it lies, without a packing copy.  `out` may be such a view too (only
+        its W-byte rows are written); without it a packed buffer of the input's shape is returned.  The result, read through its
+        strides, is bit for bit `encode_batch` of the packed copy.  CUDA tensors: one hgi_encode_u8_pitched_dev call, asynchronous
+        on the current stream; numpy arrays: hgi_encode_u8_pitched frame by frame.  Layouts, dtype, device, shape and overlap are
+        validated (ValueError) before the library is called."""
+        lay = _view_layout(images, "encode_view")
+        if out is None:
+            _view_device(images, "encode_view")
+        out, olay = _view_out(out, images, lay, "encode_view")
+        _view_device(images, "encode_view")      # (a given `out` is judged first: its faults are the caller's to see on any machine)
+        (src, b, h, w, sp, sfs, _), (dst, _, _, _, dp, dfs, _) = lay, olay
+        if b * h * w == 0:
+            return out
+        if _is_torch(images):
+            ctx = _bind_ctx(images, self._ctx)
+            _ffi.check(_ffi.lib().hgi_encode_u8_pitched_dev(ctx.handle, src, sp, w, h, self.scale_level, self._interp,
+                                                            self._lut.ctypes.data, dst, dp, b, sfs, dfs))
+            return out
+        ctx = self._ctx or _ffi.default_context(0)
+        for f in range(b):
+            _ffi.check(_ffi.lib().hgi_encode_u8_pitched(ctx.handle, src + f * sfs, sp, w, h, self.scale_level, self._interp,
+                                                        self._lut.ctypes.data, dst + f * dfs, dp))
         return out
 
     def encode_list(self, images, out=None):
@@ -323,6 +424,30 @@ class Decoder:
         out = torch.empty_like(grids) if out is None else _check_out(out, grids, "decode_batch")
         _ffi.check(_ffi.lib().hgi_decode_u8_dev(ctx.handle, grids.data_ptr(), w, h, int(levels),
                                                 self._interp, out.data_ptr(), b, h * w))
+        return out
+
+    def decode_view(self, grids, levels, out=None):
+        """Decode a VIEW of grids (see Encoder.encode_view for the layouts) into `out` -- a window of a canvas, say -- or into a
+        packed buffer.  Only the W-byte rows of `out` are written.  Bit for bit `decode_batch` of the packed copy.  CUDA tensors:
+        one hgi_decode_u8_pitched_dev call, asynchronous on the current stream; numpy arrays: hgi_decode_u8_pitched frame by
+        frame.  Validated (ValueError) before the library is called."""
+        lay = _view_layout(grids, "decode_view")
+        if out is None:
+            _view_device(grids, "decode_view")
+        out, olay = _view_out(out, grids, lay, "decode_view")
+        _view_device(grids, "decode_view")      # (a given `out` is judged first: its faults are the caller's to see on any machine)
+        (src, b, h, w, sp, sfs, _), (dst, _, _, _, dp, dfs, _) = lay, olay
+        if b * h * w == 0:
+            return out
+        if _is_torch(grids):
+            ctx = _bind_ctx(grids, self._ctx)
+            _ffi.check(_ffi.lib().hgi_decode_u8_pitched_dev(ctx.handle, src, sp, w, h, int(levels), self._interp, dst, dp, b, sfs,
+                                                            dfs))
+            return out
+        ctx = self._ctx or _ffi.default_context(0)
+        for f in range(b):
+            _ffi.check(_ffi.lib().hgi_decode_u8_pitched(ctx.handle, src + f * sfs, sp, w, h, int(levels), self._interp,
+                                                        dst + f * dfs, dp))
         return out
 
     def decode_region(self, dimensions, levels, grid, rect):

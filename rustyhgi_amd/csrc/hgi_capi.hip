@@ -12,6 +12,7 @@
 
 #include "hgi_framelist.h"
 #include "hgi_host.h"
+#include "hgi_pitched.h"
 
 using namespace hgi;
 using namespace hgi::host;
@@ -566,6 +567,114 @@ hgi_status list_impl(hgi_ctx *c, const void *const *src, const uint32_t *w, cons
     HIP_TRY(hipEventRecord(c->ev_list[slot], c->stream));
     c->list_live[slot] = true;
     HIP_TRY(e);
+    return HGI_OK;
+}
+
+// ---- pitched frames (hgi_encode_u8_pitched_dev / hgi_decode_u8_pitched_dev) ------------------------------
+// Arguments of a pitched call (include/hgi.h), everything decided before any device work.  `a` / `ap` / `as`: the input, its
+// row pitch and frame stride; `b` / `bp` / `bs`: the output's.  HGI_OK with *empty set: nothing to do.
+hgi_status check_pitched(hgi_ctx *c, const void *a, size_t ap, size_t as, const void *b, size_t bp, size_t bs, uint32_t w, uint32_t h,
+                         uint32_t levels, int interp, size_t batch, bool *empty)
+{
+    *empty = true;
+    if (!c) return fail(HGI_EINVAL, "ctx is NULL");
+    if (levels > 31) return fail(HGI_EINVAL, "levels %u out of range 0..=31", levels);
+    if (interp != HGI_INTERP_LEFTTOP && interp != HGI_INTERP_CROSSED)
+        return fail(HGI_EUNSUPPORTED, "interpolator %d not implemented (0 = LeftTop, 1 = Crossed)", interp);
+    if (c->path == HGI_PATH_LEVELWISE)
+        return fail(HGI_EUNSUPPORTED, "pitched frames run on the fused path only (this ctx is set to HGI_PATH_LEVELWISE)");
+    if (w == 0 || h == 0 || batch == 0) return HGI_OK;
+    if (!a || !b) return fail(HGI_EINVAL, "NULL buffer");
+    if (ap < w) return fail(HGI_EINVAL, "input pitch %zu < width %u", ap, w);
+    if (bp < w) return fail(HGI_EINVAL, "output pitch %zu < width %u", bp, w);
+    if (batch > 0x7fffffffu) return fail(HGI_EINVAL, "batch too large");
+    typedef unsigned __int128 u128;
+    const u128 aspan = (u128)(h - 1) * ap + w, bspan = (u128)(h - 1) * bp + w;      // bytes of one frame on either side
+    if (batch > 1 && (u128)as < aspan) return fail(HGI_EINVAL, "input frame stride %zu < (height - 1) * pitch + width", as);
+    if (batch > 1 && (u128)bs < bspan) return fail(HGI_EINVAL, "output frame stride %zu < (height - 1) * pitch + width", bs);
+    // No aliasing, tested conservatively: the byte interval the output frames span must not meet the one the input frames span
+    // (two windows interleaved in one parent allocation are refused).
+    const u128 pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    const u128 ae = pa + (u128)(batch - 1) * (batch > 1 ? as : 0) + aspan, be = pb + (u128)(batch - 1) * (batch > 1 ? bs : 0) + bspan;
+    if (ae - pa > (u128)SIZE_MAX || be - pb > (u128)SIZE_MAX) return fail(HGI_EINVAL, "frame span too large");
+    if (pb < ae && pa < be) return fail(HGI_EINVAL, "the output span overlaps the input span: they must not alias");
+    *empty = false;
+    return HGI_OK;
+}
+
+// Both sides packed (and one frame stride): the pitched call IS the uniform call -- same kernels, band order, dealing, tile heights.
+bool pitched_is_uniform(const PitchedFrames &f)
+{
+    return f.src_pitch == f.width && f.dst_pitch == f.width && (f.batch == 1 || f.src_stride == f.dst_stride);
+}
+
+// Same route per depth as encode_impl / decode_impl (split_pyramid), so the bytes are the uniform call's on the packed copy: up to
+// eight levels one launch and no scratch; from nine levels the stride-256 lattice is gathered THROUGH THE PITCH into the compact
+// planes the uniform route uses (launch_gather_view), coded there by the uniform calls -- which recurse or take the lattice
+// kernel as they would for any small image -- and the pitched cone starts from those planes.  Plane for plane what
+// ws_need_encode / ws_need_decode count.
+hgi_status pitched_decode_impl(hgi_ctx *c, const uint8_t *grid, uint8_t *img, const PitchedFrames &f, uint32_t levels, int interp)
+{
+    const size_t batch = f.batch;
+    if (levels == 0) {   // the grid is the image: a 2-D copy of the rows
+        for (size_t b = 0; b < batch; ++b)
+            HIP_TRY(hipMemcpy2DAsync(img + b * f.dst_stride, f.dst_pitch, grid + b * f.src_stride, f.src_pitch, f.width, f.height,
+                                     hipMemcpyDeviceToDevice, c->stream));
+        return HGI_OK;
+    }
+    const Split sp = split_pyramid(levels);
+    if (sp.shift) {
+        const SubGeom g = sub_geom(f.width, f.height, sp.shift);
+        uint8_t *sub_grid = ws_take(c, batch * g.stride);
+        uint8_t *sub_rec = ws_take(c, batch * g.stride);
+        if (!sub_grid || !sub_rec) return fail(HGI_ENOMEM, "scratch exhausted (lattice planes)");
+        HIP_TRY(launch_gather_view(grid, f.src_stride, f.src_pitch, sp.shift, sp.shift, g.sw, g.sh, sub_grid, g.sw, g.stride,
+                                   (uint32_t)batch, c->stream));
+        HGI_TRY(decode_impl(c, sub_grid, g.sw, g.sh, levels - sp.shift, interp, sub_rec, batch, g.stride));
+        const Seeds sd = {sub_rec, nullptr, g.sw, g.sh, g.stride, sp.up};
+        HIP_TRY(launch_decode_pitched(grid, img, f, sp.k, interp, &sd, c->stream));
+    } else if (sp.up) {
+        const Seeds sd = {nullptr, nullptr, 0, 0, 0, sp.up};
+        HIP_TRY(launch_decode_pitched(grid, img, f, sp.k, interp, &sd, c->stream));
+    } else {
+        HIP_TRY(launch_decode_pitched(grid, img, f, sp.k, interp, nullptr, c->stream));
+    }
+    return HGI_OK;
+}
+
+hgi_status pitched_encode_impl(hgi_ctx *c, const uint8_t *img, uint8_t *grid, const PitchedFrames &f, uint32_t levels, int interp,
+                               const uint8_t lut[256])
+{
+    const size_t batch = f.batch;
+    if (levels == 0) {   // src/encoder.rs:28-36 with step 1: the grid is the image
+        for (size_t b = 0; b < batch; ++b)
+            HIP_TRY(hipMemcpy2DAsync(grid + b * f.dst_stride, f.dst_pitch, img + b * f.src_stride, f.src_pitch, f.width, f.height,
+                                     hipMemcpyDeviceToDevice, c->stream));
+        return HGI_OK;
+    }
+    const Lut256 l = pack_lut(lut);
+    const bool ident = is_identity(lut);
+    const Split sp = split_pyramid(levels);
+    if (sp.shift) {
+        // the lattice = 0 (mod 2^shift) first: its reconstruction and residuals are what the tile launch starts from (the tile
+        // kernel puts the residuals into the pitched grid, as the uniform route puts them into the packed one)
+        const SubGeom g = sub_geom(f.width, f.height, sp.shift);
+        uint8_t *sub_img = ws_take(c, batch * g.stride);
+        uint8_t *sub_grid = ws_take(c, batch * g.stride);
+        uint8_t *sub_rec = ws_take(c, batch * g.stride);
+        if (!sub_img || !sub_grid || !sub_rec) return fail(HGI_ENOMEM, "scratch exhausted (lattice planes)");
+        HIP_TRY(launch_gather_view(img, f.src_stride, f.src_pitch, sp.shift, sp.shift, g.sw, g.sh, sub_img, g.sw, g.stride,
+                                   (uint32_t)batch, c->stream));
+        HGI_TRY(encode_impl(c, sub_img, g.sw, g.sh, levels - sp.shift, interp, lut, sub_grid, batch, g.stride));
+        HGI_TRY(decode_impl(c, sub_grid, g.sw, g.sh, levels - sp.shift, interp, sub_rec, batch, g.stride));
+        const Seeds sd = {sub_rec, sub_grid, g.sw, g.sh, g.stride, sp.up};
+        HIP_TRY(launch_encode_pitched(img, grid, f, sp.k, interp, l, ident, &sd, c->stream));
+    } else if (sp.up) {
+        const Seeds sd = {nullptr, nullptr, 0, 0, 0, sp.up};
+        HIP_TRY(launch_encode_pitched(img, grid, f, sp.k, interp, l, ident, &sd, c->stream));
+    } else {
+        HIP_TRY(launch_encode_pitched(img, grid, f, sp.k, interp, l, ident, nullptr, c->stream));
+    }
     return HGI_OK;
 }
 
@@ -1160,6 +1269,82 @@ hgi_status hgi_decode_scaled_u8(hgi_ctx *c, const uint8_t *grid, uint32_t w, uin
     HIP_TRY(hipMemcpy2DAsync(out, out_pitch, d_out, sw, sw, sh, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return HGI_OK;
+}
+
+// Pitched frames: both pitches equal to the width forward to the uniform calls; otherwise the pitched kernels
+// (hgi_fused_pitched_*.hip), routed per depth like the uniform calls.
+hgi_status hgi_encode_u8_pitched_dev(hgi_ctx *c, const void *d_img, size_t img_pitch, uint32_t w, uint32_t h, uint32_t levels,
+                                     hgi_interp interp, const uint8_t lut[256], void *d_grid, size_t grid_pitch, size_t batch,
+                                     size_t img_frame_stride, size_t grid_frame_stride)
+{
+    bool empty;
+    HGI_TRY(check_pitched(c, d_img, img_pitch, img_frame_stride, d_grid, grid_pitch, grid_frame_stride, w, h, levels, interp, batch, &empty));
+    if (!lut) return fail(HGI_EINVAL, "lut is NULL");
+    if (empty) return HGI_OK;
+    const PitchedFrames f = {w, h, (uint32_t)batch, (uint64_t)img_pitch, (uint64_t)grid_pitch, batch > 1 ? (uint64_t)img_frame_stride : 0,
+                             batch > 1 ? (uint64_t)grid_frame_stride : 0};
+    if (pitched_is_uniform(f)) return hgi_encode_u8_dev(c, d_img, w, h, levels, interp, lut, d_grid, batch, img_frame_stride);
+    HIP_TRY(hipSetDevice(c->device));
+    // the uniform call's scratch (none up to eight levels): a ctx reserved for the frame's shape allocates nothing here
+    HGI_TRY(ws_ensure(c, ws_need(c, w, h, levels, batch, (size_t)w * h)));
+    c->ws_used = 0;
+    return pitched_encode_impl(c, static_cast<const uint8_t *>(d_img), static_cast<uint8_t *>(d_grid), f, levels, interp, lut);
+}
+
+hgi_status hgi_decode_u8_pitched_dev(hgi_ctx *c, const void *d_grid, size_t grid_pitch, uint32_t w, uint32_t h, uint32_t levels,
+                                     hgi_interp interp, void *d_img, size_t img_pitch, size_t batch, size_t grid_frame_stride,
+                                     size_t img_frame_stride)
+{
+    bool empty;
+    HGI_TRY(check_pitched(c, d_grid, grid_pitch, grid_frame_stride, d_img, img_pitch, img_frame_stride, w, h, levels, interp, batch, &empty));
+    if (empty) return HGI_OK;
+    const PitchedFrames f = {w, h, (uint32_t)batch, (uint64_t)grid_pitch, (uint64_t)img_pitch, batch > 1 ? (uint64_t)grid_frame_stride : 0,
+                             batch > 1 ? (uint64_t)img_frame_stride : 0};
+    if (pitched_is_uniform(f)) return hgi_decode_u8_dev(c, d_grid, w, h, levels, interp, d_img, batch, grid_frame_stride);
+    HIP_TRY(hipSetDevice(c->device));
+    HGI_TRY(ws_ensure(c, ws_need(c, w, h, levels, batch, (size_t)w * h)));
+    c->ws_used = 0;
+    return pitched_decode_impl(c, static_cast<const uint8_t *>(d_grid), static_cast<uint8_t *>(d_img), f, levels, interp);
+}
+
+// One frame in host memory.  The host calls are transfer-bound: the width-byte rows go up with one 2-D copy into a
+// packed plane, the uniform route codes it, and the width-byte rows of the result come down with one 2-D copy -- the bytes
+// between the caller's rows are neither read nor written.  Sized by host_call_need, the formula hgi_ctx_reserve uses.
+static hgi_status host_pitched(hgi_ctx *c, const uint8_t *in, size_t in_pitch, uint8_t *out, size_t out_pitch, uint32_t w, uint32_t h,
+                               uint32_t levels, hgi_interp interp, const uint8_t *lut, bool encode)
+{
+    bool empty;
+    HGI_TRY(check_pitched(c, in, in_pitch, 0, out, out_pitch, 0, w, h, levels, interp, 1, &empty));
+    if (encode && !lut) return fail(HGI_EINVAL, "lut is NULL");
+    if (empty) return HGI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)w * h;
+    const size_t slot = align_up(n, 256) + 256;
+    const size_t need = host_call_need(c, w, h, levels), flat = 2 * slot + ws_need(c, w, h, levels, 1, n);
+    HGI_TRY(ws_ensure(c, need > flat ? need : flat));
+    c->ws_used = 0;
+    uint8_t *d_in = ws_take(c, n), *d_out = ws_take(c, n);
+    if (!d_in || !d_out) return fail(HGI_ENOMEM, "scratch exhausted (host staging)");
+    HIP_TRY(hipMemcpy2DAsync(d_in, w, in, in_pitch, w, h, hipMemcpyHostToDevice, c->stream));
+    if (encode)
+        HGI_TRY(encode_impl(c, d_in, w, h, levels, interp, lut, d_out, 1, n));
+    else
+        HGI_TRY(decode_impl(c, d_in, w, h, levels, interp, d_out, 1, n));
+    HIP_TRY(hipMemcpy2DAsync(out, out_pitch, d_out, w, w, h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return HGI_OK;
+}
+
+hgi_status hgi_encode_u8_pitched(hgi_ctx *c, const uint8_t *img, size_t img_pitch, uint32_t w, uint32_t h, uint32_t levels,
+                                 hgi_interp interp, const uint8_t lut[256], uint8_t *grid_out, size_t grid_pitch)
+{
+    return host_pitched(c, img, img_pitch, grid_out, grid_pitch, w, h, levels, interp, lut, true);
+}
+
+hgi_status hgi_decode_u8_pitched(hgi_ctx *c, const uint8_t *grid, size_t grid_pitch, uint32_t w, uint32_t h, uint32_t levels,
+                                 hgi_interp interp, uint8_t *img_out, size_t img_pitch)
+{
+    return host_pitched(c, grid, grid_pitch, img_out, img_pitch, w, h, levels, interp, nullptr, false);
 }
 
 // Frame lists: levels 1 ... 8 in one launch over the tiles of every frame (hgi_fused_list_*.hip); levels 0 and from nine on

@@ -114,6 +114,16 @@ hipError_t launch_decode_list(const ListArgs &a, uint32_t max_width, uint32_t k,
 hipError_t launch_encode_list(const ListArgs &a, uint32_t k, int interp, const Lut256 &lut, bool ident, const Seeds *seeds,
                               hipStream_t s);
 
+// ---- pitched frames (hgi_fused_pitched_dec.hip / hgi_fused_pitched_enc.hip): rows `pitch` >= width bytes apart, a pitch of
+// its own on each side.  PitchedFrames (hgi_pitched.h): shape, pitches, frame strides.  Only the width bytes of each output row
+// are written.  k = fused levels (1 ... kFusedMaxLevels); seeds: none, or the cone (k == 4, up >= 1; with planes of the
+// stride-256 lattice for deeper pyramids).
+struct PitchedFrames;
+hipError_t launch_decode_pitched(const uint8_t *grid, uint8_t *img, const PitchedFrames &f, uint32_t k, int interp, const Seeds *seeds,
+                                 hipStream_t s);
+hipError_t launch_encode_pitched(const uint8_t *img, uint8_t *grid, const PitchedFrames &f, uint32_t k, int interp, const Lut256 &lut,
+                                 bool ident, const Seeds *seeds, hipStream_t s);
+
 // dst[f][j][i] = src[f][j << k][i << k]  (the stride-2^k lattice as a dense plane)
 hipError_t launch_gather_lattice(const uint8_t *src, const Frames &f, uint32_t k, uint8_t *dst,
                                  uint32_t sw, uint32_t sh, uint64_t dst_stride, hipStream_t s);
