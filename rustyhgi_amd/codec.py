@@ -242,9 +242,10 @@ def _view_layout(x, what):
     return ptr, b, h, w, pitch, (sf if b > 1 else span), span
 
 
-def _view_out(out, like, lay, what):
-    """`out=` of a view call: None (a packed buffer of the input's shape is allocated beside it) or a view of the input's kind,
-    shape and device whose byte span does not meet the input's.  Returns (out, its layout)."""
+def _view_out(out, like, lay, what, name="out"):
+    """`out=` of a view call (or the output argument called `name`): None (a packed buffer of the input's shape is allocated
+    beside it) or a view of the input's kind, shape and device whose byte span does not meet the input's.  Returns (out, its
+    layout)."""
     if out is None:
         if _is_torch(like):
             import torch
@@ -253,18 +254,18 @@ def _view_out(out, like, lay, what):
             out = np.empty(like.shape, np.uint8)
         return out, _view_layout(out, what)
     if _is_torch(like) != _is_torch(out):
-        raise ValueError("%s: `out` must be a %s like the input" % (what, "torch tensor" if _is_torch(like) else "numpy array"))
-    olay = _view_layout(out, what + " (out)")
+        raise ValueError("%s: `%s` must be a %s like the input" % (what, name, "torch tensor" if _is_torch(like) else "numpy array"))
+    olay = _view_layout(out, "%s (%s)" % (what, name))
     if tuple(out.shape) != tuple(like.shape):
-        raise ValueError("%s: `out` has shape %s, the input %s" % (what, tuple(out.shape), tuple(like.shape)))
+        raise ValueError("%s: `%s` has shape %s, the input %s" % (what, name, tuple(out.shape), tuple(like.shape)))
     if _is_torch(like):
         if out.device != like.device:
-            raise ValueError("%s: `out` lives on %s, the input on %s" % (what, out.device, like.device))
+            raise ValueError("%s: `%s` lives on %s, the input on %s" % (what, name, out.device, like.device))
     elif not out.flags["WRITEABLE"]:
-        raise ValueError("%s: `out` is not writable" % what)
+        raise ValueError("%s: `%s` is not writable" % (what, name))
     (a0, ab, _, _, _, afs, aspan), (b0, bb, _, _, _, bfs, bspan) = lay, olay
     if ab and a0 < b0 + (bb - 1) * bfs + bspan and b0 < a0 + (ab - 1) * afs + aspan:
-        raise ValueError("%s: `out` shares memory with the input (byte spans, tested conservatively)" % what)
+        raise ValueError("%s: `%s` shares memory with the input (byte spans, tested conservatively)" % (what, name))
     return out, olay
 
 
@@ -358,6 +359,56 @@ class Encoder:
             _ffi.check(_ffi.lib().hgi_encode_u8_pitched(ctx.handle, src + f * sfs, sp, w, h, self.scale_level, self._interp,
                                                         self._lut.ctypes.data, dst + f * dfs, dp))
         return out
+
+    def encode_with_reconstruction(self, images, out=None, recon=None):
+        """Encode a view AND return the image the decoder will make of the grid: `(grid, recon)`, where `grid` is bit for bit
+        `encode_view(images)` and `recon` bit for bit `Decoder.decode_view(grid, scale_level)` -- what the reference's
+        `Encoder::encode` leaves in its input (src/encoder.rs:63-64).  `images`, `out` and `recon` are views as for `encode_view`
+        ((H, W) or (B, H, W), any row stride >= W); only the W-byte rows of the two outputs are written, the input is not
+        modified, and none of the three may share memory with another.  CUDA tensors: ONE hgi_recon_encode_u8_dev launch
+        (libhgi_recon.so), asynchronous on the current stream -- 3 B/px instead of the 4 B/px of encode + decode.  What that
+        launch does not serve (HGI_EUNSUPPORTED: 0 or more than 8 levels, offsets beyond 32 bits, a width that is no multiple
+        of 4 with the input's last bytes at the end of a 4-KiB page) is composed from `encode_view` + `decode_view` on the same
+        stream: the same bytes, not fused.  numpy arrays are uploaded and downloaded through torch tensors, synchronously.
+        Validated (ValueError) before any device call; empty inputs need no device."""
+        what = "encode_with_reconstruction"
+        lay = _view_layout(images, what)
+        if out is None and recon is None:
+            _view_device(images, what)
+        out, olay = _view_out(out, images, lay, what)
+        recon, rlay = _view_out(recon, images, lay, what, name="recon")
+        (g0, gb, _, _, _, gfs, gspan), (r0, _, _, _, _, rfs, rspan) = olay, rlay
+        if gb and g0 < r0 + (gb - 1) * rfs + rspan and r0 < g0 + (gb - 1) * gfs + gspan:
+            raise ValueError("%s: `recon` shares memory with `out` (byte spans, tested conservatively)" % what)
+        _view_device(images, what)
+        (src, b, h, w, sp, sfs, _) = lay
+        if b * h * w == 0:
+            return out, recon
+        if not _is_torch(images):
+            import torch
+            if not torch.cuda.is_available():
+                raise _ffi.HgiError(_ffi.EDEVICE, "%s needs a GPU (there is no CPU fallback)" % what)
+            dev = self._ctx.device if self._ctx is not None else 0
+            t = torch.from_numpy(np.ascontiguousarray(images)).to("cuda:%d" % dev)
+            g, r = self.encode_with_reconstruction(t)
+            out[...] = g.cpu().numpy()
+            recon[...] = r.cpu().numpy()
+            return out, recon
+        import torch
+        from . import _ffi_recon
+        dev = images.device.index if images.device.index is not None else torch.cuda.current_device()
+        if self._ctx is not None and self._ctx.device != dev:      # both routes judge the Encoder's context alike (_bind_ctx)
+            raise ValueError("tensor lives on cuda:%d but the context was created for cuda:%d" % (dev, self._ctx.device))
+        with torch.cuda.device(dev):
+            st = _ffi_recon.lib().hgi_recon_encode_u8_dev(
+                _ffi._vp(torch.cuda.current_stream(dev).cuda_stream or 0), src, sp, w, h, self.scale_level, self._interp,
+                self._lut.ctypes.data, olay[0], olay[4], rlay[0], rlay[4], b, sfs, olay[5], rlay[5])
+        if st == _ffi.EUNSUPPORTED:      # not served by the one launch: the same bytes from two calls
+            self.encode_view(images, out=out)
+            Decoder(self.interpolator, context=self._ctx).decode_view(out, self.scale_level, out=recon)
+            return out, recon
+        _ffi_recon.check(st)
+        return out, recon
 
     def encode_list(self, images, out=None):
         """A list of (h_i, w_i) uint8 frames of any shapes -> the list of their residual planes.  CUDA tensors (one device,
