@@ -274,6 +274,74 @@ def _view_device(x, what):
         raise ValueError("%s: torch tensors must live on the GPU (use numpy for host buffers)" % what)
 
 
+def _typed_view_layout(x, what, dtype, esize):
+    """_view_layout's sibling for the output of a mapped decode: a (height, width) or (batch, height, width) view of `dtype`
+    elements, `esize` bytes each, whose last dimension has stride 1 ELEMENT, whose rows lie >= width elements apart and whose
+    frames lie >= one frame's span apart.  Returns (ptr, batch, height, width, pitch, frame_stride, span) with pitch, stride and
+    span in BYTES, span = (height - 1) * pitch + width * esize.  Nothing here touches a device."""
+    if _is_torch(x):
+        if x.dtype != dtype:
+            raise ValueError("%s: expected a %s tensor, not %s" % (what, dtype, x.dtype))
+        shape, strides = tuple(int(v) for v in x.shape), tuple(int(v) for v in x.stride())
+    elif isinstance(x, np.ndarray):
+        if x.dtype != dtype:
+            raise ValueError("%s: expected a %s array, not %s" % (what, dtype, x.dtype))
+        if any(int(v) % esize for v in x.strides):
+            raise ValueError("%s: strides %s are not whole elements" % (what, x.strides))
+        shape, strides = tuple(int(v) for v in x.shape), tuple(int(v) // esize for v in x.strides)
+    else:
+        raise ValueError("%s: expected a torch CUDA tensor or numpy array of %s" % (what, dtype))
+    if len(shape) not in (2, 3):
+        raise ValueError("%s: expected a (height, width) or (batch, height, width) view, not %d dimensions" % (what, len(shape)))
+    if len(shape) == 2:
+        shape, strides = (1,) + shape, (0,) + strides
+    (b, h, w), (sf, sr, sc) = shape, strides
+    if max(shape) >= 2 ** 32:
+        raise ValueError("%s: the view is too large" % what)
+    if b * h * w == 0:
+        return 0, b, h, w, w * esize, h * w * esize, h * w * esize
+    ptr = x.data_ptr() if _is_torch(x) else x.ctypes.data
+    if w > 1 and sc != 1:
+        raise ValueError("%s: the last dimension must have stride 1, not %d" % (what, sc))
+    if h > 1 and sr < w:
+        raise ValueError("%s: the row stride %d is smaller than the width %d" % (what, sr, w))
+    pitch = sr if h > 1 else w
+    span = (h - 1) * pitch + w
+    if b > 1 and sf < span:
+        raise ValueError("%s: the frame stride %d is smaller than a frame's span %d" % (what, sf, span))
+    return ptr, b, h, w, pitch * esize, (sf if b > 1 else span) * esize, span * esize
+
+
+def _map_table(table, grids, what):
+    """The table of a mapped decode: 256 contiguous elements of 2 or 4 bytes -- a 1-D torch tensor on the grids' device, or a
+    numpy array (torch grids: uploaded per call).  Returns (dtype of the output, element size, byte range or None)."""
+    if _is_torch(table):
+        if not _is_torch(grids):
+            raise ValueError("%s: a torch `table` goes with torch grids (numpy grids take a numpy table)" % what)
+        if table.dim() != 1 or table.numel() != 256 or not table.is_contiguous():
+            raise ValueError("%s: `table` must be a contiguous 1-D tensor of 256 elements, not shape %s" % (what, tuple(table.shape)))
+        esize = int(table.element_size())
+        if esize not in (2, 4) or table.is_complex():
+            raise ValueError("%s: `table` elements must be 2 or 4 bytes, not %s" % (what, table.dtype))
+        if table.device != grids.device:
+            raise ValueError("%s: `table` lives on %s, the grids on %s" % (what, table.device, grids.device))
+        return table.dtype, esize, (table.data_ptr(), table.data_ptr() + 256 * esize)
+    if not isinstance(table, np.ndarray):
+        raise ValueError("%s: `table` must be a torch tensor or numpy array of 256 elements" % what)
+    if table.ndim != 1 or table.shape[0] != 256 or not table.flags["C_CONTIGUOUS"]:
+        raise ValueError("%s: `table` must be a contiguous 1-D array of 256 elements, not shape %s" % (what, table.shape))
+    esize = int(table.dtype.itemsize)
+    if esize not in (2, 4) or table.dtype.kind not in "fiu":
+        raise ValueError("%s: `table` elements must be 2 or 4 bytes, not %s" % (what, table.dtype))
+    if _is_torch(grids):
+        import torch
+        try:
+            return torch.from_numpy(np.empty(0, table.dtype)).dtype, esize, None
+        except TypeError:
+            raise ValueError("%s: torch has no dtype for a %s `table`: pass a tensor" % (what, table.dtype))
+    return table.dtype, esize, (table.ctypes.data, table.ctypes.data + 256 * esize)
+
+
 def _np_image(a):
     a = np.ascontiguousarray(a, dtype=np.uint8)
     if a.ndim != 2:
@@ -617,3 +685,81 @@ class Decoder:
         ins, ws, hs, ptrs = _list_arrays(frames, outs)
         _ffi.check(_ffi.lib().hgi_decode_u8_list_dev(ctx.handle, ins, ws, hs, int(levels), self._interp, ptrs, len(frames)))
         return outs
+
+    def decode_mapped(self, grids, levels, table, out=None):
+        """Decode a view of grids straight into frames of the `table`'s dtype: `out[..., y, x] = table[decoded[..., y, x]]`,
+        `decoded` being `decode_view(grids, levels)` -- float16 / bfloat16 / float32 frames, normalised however the table says
+        (`rustyhgi_amd.affine_table`), without the uint8 image ever reaching memory.  `grids` is a view as for `decode_view`;
+        `table` holds 256 elements of a 2- or 4-byte dtype: a 1-D contiguous torch CUDA tensor on the grids' device, or a numpy
+        array (a dtype numpy lacks, such as bfloat16, needs a tensor).  A numpy table is uploaded on every call: the hot path
+        keeps the table on the device and passes that tensor.  The result has the table's dtype and the grids' shape; `out` may
+        be a view of that dtype (last stride 1 element, any row stride >= W elements) of which only the W-element rows are
+        written.  The library copies the table's bits and does no arithmetic (NaN patterns and signed zeros come through).
+        CUDA tensors: ONE hgi_map_decode_dev launch (libhgi_map.so), asynchronous on the current stream -- 1 + E B/px instead of
+        the 3 + E B/px of a decode and a conversion.  What that launch does not serve (HGI_EUNSUPPORTED: 0 or more than 8
+        levels, offsets beyond 32 bits, a width that is no multiple of 4 with the grids' last bytes at the end of a 4-KiB page)
+        is composed from `decode_view` into a temporary and a gather on the same stream: the same bits, not fused.  numpy grids
+        are uploaded and downloaded through torch tensors, synchronously; without a GPU that raises HgiError(EDEVICE).
+        Validated (ValueError) before any device call; empty inputs need no device."""
+        what = "decode_mapped"
+        lay = _view_layout(grids, what)
+        dtype, esize, tspan = _map_table(table, grids, what)
+        (src, b, h, w, sp, sfs, gspan) = lay
+        if out is None:
+            _view_device(grids, what)
+            if _is_torch(grids):
+                import torch
+                out = torch.empty(tuple(grids.shape), dtype=dtype, device=grids.device)
+            else:
+                out = np.empty(grids.shape, dtype)
+            olay = _typed_view_layout(out, what, dtype, esize)
+        else:
+            if _is_torch(grids) != _is_torch(out):
+                raise ValueError("%s: `out` must be a %s like the grids" % (what, "torch tensor" if _is_torch(grids) else "numpy array"))
+            olay = _typed_view_layout(out, "%s (out)" % what, dtype, esize)
+            if tuple(out.shape) != tuple(grids.shape):
+                raise ValueError("%s: `out` has shape %s, the grids %s" % (what, tuple(out.shape), tuple(grids.shape)))
+            if _is_torch(grids):
+                if out.device != grids.device:
+                    raise ValueError("%s: `out` lives on %s, the grids on %s" % (what, out.device, grids.device))
+            elif not out.flags["WRITEABLE"]:
+                raise ValueError("%s: `out` is not writable" % what)
+        (dst, _, _, _, dp, dfs, ospan) = olay
+        if b * h * w:
+            g_lo, g_hi = src, src + (b - 1) * sfs + gspan
+            o_lo, o_hi = dst, dst + (b - 1) * dfs + ospan
+            if g_lo < o_hi and o_lo < g_hi:
+                raise ValueError("%s: `out` shares memory with the grids (byte spans, tested conservatively)" % what)
+            if tspan is not None and tspan[0] < o_hi and o_lo < tspan[1]:
+                raise ValueError("%s: `out` shares memory with `table`" % what)
+            if tspan is not None and tspan[0] < g_hi and g_lo < tspan[1]:
+                raise ValueError("%s: `table` shares memory with the grids" % what)
+        _view_device(grids, what)
+        if b * h * w == 0:
+            return out
+        import torch
+        bits = {2: (np.int16, torch.int16), 4: (np.int32, torch.int32)}[esize]      # elements travel as their bit patterns
+        if not _is_torch(grids):
+            if not torch.cuda.is_available():
+                raise _ffi.HgiError(_ffi.EDEVICE, "%s needs a GPU (there is no CPU fallback)" % what)
+            dev = "cuda:%d" % (self._ctx.device if self._ctx is not None else 0)
+            g = torch.from_numpy(np.ascontiguousarray(grids)).to(dev)
+            t = torch.from_numpy(table.view(bits[0])).to(dev)
+            out.view(bits[0])[...] = self.decode_mapped(g, levels, t).cpu().numpy().reshape(out.shape)
+            return out
+        from . import _ffi_map
+        dev = grids.device.index if grids.device.index is not None else torch.cuda.current_device()
+        if self._ctx is not None and self._ctx.device != dev:      # both routes judge the Decoder's context alike (_bind_ctx)
+            raise ValueError("tensor lives on cuda:%d but the context was created for cuda:%d" % (dev, self._ctx.device))
+        if not _is_torch(table):
+            table = torch.from_numpy(table).to(grids.device)
+        with torch.cuda.device(dev):
+            st = _ffi_map.lib().hgi_map_decode_dev(
+                _ffi._vp(torch.cuda.current_stream(dev).cuda_stream or 0), src, sp, w, h, int(levels), self._interp,
+                table.data_ptr(), esize, dst, dp, b, sfs, dfs)
+        if st == _ffi.EUNSUPPORTED:      # not served by the one launch: the same bits from a decode and a gather
+            tmp = self.decode_view(grids, levels)
+            out.view(bits[1]).copy_(table.view(bits[1])[tmp.long()])
+            return out
+        _ffi_map.check(st)
+        return out
