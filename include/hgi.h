@@ -184,7 +184,7 @@ HGI_API hgi_status hgi_decode_scaled_u8_dev(hgi_ctx *ctx, const void *d_grid, ui
                                             uint32_t levels, hgi_interp interp, uint32_t shift, void *d_out,
                                             size_t out_pitch, size_t batch, size_t frame_stride, size_t out_frame_stride);
 /* One frame in host memory.  Synchronous.  Only the sh grid rows the lattice lies on are uploaded      */
-/* (one 2-D copy), only the sw x sh result comes back: row j goes to out + j * out_pitch.  Same         */
+/* (gathered, one copy), only the sw x sh result comes back: row j goes to out + j * out_pitch.  Same   */
 /* argument rules as above with batch = 1; hgi_ctx_reserve for the frame's shape covers its scratch.    */
 HGI_API hgi_status hgi_decode_scaled_u8(hgi_ctx *ctx, const uint8_t *grid, uint32_t width, uint32_t height,
                                         uint32_t levels, hgi_interp interp, uint32_t shift, uint8_t *out, size_t out_pitch);

@@ -1264,9 +1264,23 @@ hgi_status hgi_decode_scaled_u8(hgi_ctx *c, const uint8_t *grid, uint32_t w, uin
     const size_t cn = (size_t)w * sh;
     uint8_t *d_in = ws_take(c, cn), *d_out = ws_take(c, (size_t)sw * sh);
     if (!d_in || !d_out) return fail(HGI_ENOMEM, "scratch exhausted (host staging)");
-    HIP_TRY(hipMemcpy2DAsync(d_in, w, grid, (size_t)w << shift, w, sh, hipMemcpyHostToDevice, c->stream));
+    // The rows the lattice lies on are w << shift bytes apart in the caller's grid, and the last of them is followed by fewer
+    // bytes than that: a 2-D copy of sh rows at that pitch describes a source rectangle that reaches up to (w << shift) - w bytes
+    // past the end of the caller's array -- pageable memory the runtime may pin and read as a whole (seen as an illegal memory
+    // access when the array ended at the top of the heap).  So the rows are gathered on the host and go up as one compact block,
+    // before this call returns to the stream's work; every byte read lies inside [grid, grid + w * h).
+    if (shift == 0) {
+        HIP_TRY(hipMemcpyAsync(d_in, grid, cn, hipMemcpyHostToDevice, c->stream));
+    } else {
+        std::vector<uint8_t> rows(cn);
+        for (uint32_t j = 0; j < sh; ++j) memcpy(rows.data() + (size_t)j * w, grid + (((size_t)j << shift) * w), w);
+        HIP_TRY(hipStreamSynchronize(c->stream));      // (the scratch may still be read by earlier work of the stream)
+        HIP_TRY(hipMemcpy(d_in, rows.data(), cn, hipMemcpyHostToDevice));
+    }
     HGI_TRY(scaled_impl(c, d_in, w, h, (uint64_t)w, cn, levels, interp, shift, d_out, sw, 1, cn, 0));
-    HIP_TRY(hipMemcpy2DAsync(out, out_pitch, d_out, sw, sw, sh, hipMemcpyDeviceToHost, c->stream));
+    // ... and the same on the way down: the last output row is followed by sw bytes only, not by out_pitch
+    if (sh > 1) HIP_TRY(hipMemcpy2DAsync(out, out_pitch, d_out, sw, sw, sh - 1, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out + (size_t)(sh - 1) * out_pitch, d_out + (size_t)(sh - 1) * sw, sw, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return HGI_OK;
 }

@@ -31,6 +31,7 @@
 #include "hgi_dev.h"
 #include "hgi_fastdiv.h"
 #include "hgi_knobs.h"
+#include "hgi_tilewalk.h"
 
 namespace hgi {
 namespace {
@@ -131,9 +132,6 @@ static_assert(TH != 64 || 18 * (buf_bytes(4) + rbuf_bytes(4) + 256) <= 160 * 102
 #endif
 #ifndef HGI_DEC_REVERSE_DEFAULT
 #define HGI_DEC_REVERSE_DEFAULT 0
-#endif
-#ifndef HGI_TILE_ORDER
-#define HGI_TILE_ORDER 0      // order of the interior tiles inside a frame: 0 row-major (experiment), 3 column-major bands (shipped; set by the direction's unit)
 #endif
 #ifndef HGI_TILE_BAND
 #define HGI_TILE_BAND 8
@@ -281,11 +279,7 @@ struct Tile {
     u32 frame, X0, Y0;
 };
 
-// XCD-aware block -> tile map.  Workgroups are dealt round-robin over the 8 XCDs (b % 8 labels the XCD a
-// block runs on), so XCD x gets the x-th contiguous eighth of the row-major tile list: x-neighbours
-// (which share halo lines) and consecutive tile rows land in the same XCD's L2.  Speed only, never
-// correctness.
-__device__ __forceinline__ u32 range_first(u32 ntiles, u32 x) { return x * (ntiles >> 3) + (x < (ntiles & 7u) ? x : (ntiles & 7u)); }
+// (range_first -- the XCD-aware block -> tile map: hgi_tilewalk.h)
 
 // Compile-time ordering point for the wave's LDS traffic.  A wave's LDS instructions execute in
 // order, so a ds_read issued after a ds_write sees it without any wait; the compiler only has to be
@@ -1230,79 +1224,26 @@ __device__ __forceinline__ Buf make_buf(const u8 *fr, u8 *out, u32 W, u32 H, Til
 // ---------------------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------------------
-// Tile lists.  `full_x` x `full_y` tiles per frame lie entirely inside the image: the fast kernels walk
-// those; the checked path takes the rest (right column first, then the bottom rows).
-// (FastDiv / make_fastdiv / fdiv: hgi_fastdiv.h -- the block -> tile index math divides by launch-wide constants only)
-struct TileGrid {
-    u32 tiles_x, tiles_y;   // all tiles of a frame
-    u32 full_x, full_y;     // tiles whose body is inside the image (0 x 0 when the fast path is off)
-    u32 nfast, nedge;       // totals over the batch
-    u32 reverse;            // walk the interior tile list backwards (speed only: see launch_decode_fused)
-    u32 band;               // tile rows per band of the column-major walk (fast_tile)
-    u32 xmode;              // how the band-ordered tile list is dealt to the XCDs (block_role)
-    // derived by finish_grid() on the host, so that the kernels neither divide nor re-derive launch constants:
-    u32 ex, nf;             // interior tile columns / interior tiles the walk runs on
-    u32 tpf, P, nfull, rem_rows;   // tiles per frame; per band; in a frame's whole bands; rows of its last, shorter band
-    u32 rr_own, rr_tail0;   // round-robin dealing: blocks per XCD that belong to whole rounds of eight bands; first tile behind them
-    FastDiv fd_tpf, fd_P, fd_band, fd_rem, fd_ex;
-#ifdef HGI_TIMELINE
-    u64 *timeline;          // experiment builds (tools/timeline.py): eight u64 per block -- start, staged, end, hardware id, entry
-#endif
-};
-
+// Tile lists, the launch constants derived from them and the block -> tile index arithmetic: hgi_tilewalk.h (TileGrid,
+// finish_grid, walk_block_role, walk_fast_tile, walk_edge_tile -- plain C++, walked on the CPU by tests/cpp/test_tilewalk.cpp).
 __device__ __forceinline__ Tile fast_tile(u32 t, const TileGrid &g)
 {
-    t = __builtin_amdgcn_readfirstlane(g.reverse ? g.nf - 1u - t : t);
+    t = __builtin_amdgcn_readfirstlane(walk_position(t, g));
+    const WalkTile w = walk_fast_tile(t, g);
     Tile tl;
-    tl.frame = fdiv(t, g.fd_tpf);
-    const u32 tt = t - tl.frame * g.tpf;
-    u32 ty, tx;
-#if HGI_TILE_ORDER == 0          // row-major (experiment)
-    ty = fdiv(tt, g.fd_ex);
-    tx = tt - ty * g.ex;
-#else
-    // Bands of g.band tile rows, column-major inside a band: x-neighbours are dispatched `rows` tiles apart,
-    // y-neighbours next to each other.  The last band of a frame takes the rows that are left.
-    {
-        u32 rows, row0, r;
-        if (tt < g.nfull) {
-            const u32 band = fdiv(tt, g.fd_P);
-            r = tt - band * g.P;
-            row0 = band * g.band;
-            rows = g.band;
-            tx = fdiv(r, g.fd_band);
-        } else {
-            rows = g.rem_rows;
-            r = tt - g.nfull;
-            row0 = g.full_y - rows;
-            tx = fdiv(r, g.fd_rem);
-        }
-        ty = row0 + (r - tx * rows);
-    }
-#endif
-    tl.X0 = tx * TW;
-    tl.Y0 = ty * TH;
+    tl.frame = w.frame;
+    tl.X0 = w.tx * TW;
+    tl.Y0 = w.ty * TH;
     return tl;
 }
 
 __device__ __forceinline__ Tile edge_tile(u32 e, const TileGrid &g)
 {
-    const u32 right = (g.tiles_x - g.full_x) * g.tiles_y;          // tiles with tx >= full_x
-    const u32 epf = right + g.full_x * (g.tiles_y - g.full_y);     // + tiles with ty >= full_y, tx < full_x
+    const WalkTile w = walk_edge_tile(e, g);
     Tile tl;
-    tl.frame = e / epf;
-    u32 i = e - tl.frame * epf, tx, ty;
-    if (i < right) {
-        const u32 w = g.tiles_x - g.full_x;
-        ty = i / w;
-        tx = g.full_x + (i - ty * w);
-    } else {
-        i -= right;
-        ty = g.full_y + i / g.full_x;
-        tx = i % g.full_x;
-    }
-    tl.X0 = tx * TW;
-    tl.Y0 = ty * TH;
+    tl.frame = w.frame;
+    tl.X0 = w.tx * TW;
+    tl.Y0 = w.ty * TH;
     return tl;
 }
 
@@ -1602,42 +1543,8 @@ __device__ __forceinline__ void dec_tile_edge(u8 *buf, const TileCtx &cur, const
     dec_fine_fast<INTERP, EDGE>(buf, cur.b, odd, rows, cols);
 }
 
-// One block (= one wave) per tile, ONE launch per batch.  The first blocks take the ragged tiles
-// (their count padded to a multiple of 8 so that b % 8 keeps labelling the XCD), so the slow tiles
-// start first and overlap the interior ones; the interior tiles follow in XCD-contiguous order.
-// (A persistent variant -- resident waves pulling tiles from per-XCD atomic counters and prefetching
-// the next tile into registers -- was built and measured: not faster on MI355X, see DESIGN.md
-// "Scheduling".)
-struct BlockRole {
-    bool edge, idle;
-    u32 index;       // edge tile index, or position of the interior tile in the XCD-contiguous order
-};
-
-__device__ __forceinline__ BlockRole block_role(const TileGrid &g)
-{
-    const u32 b = blockIdx.x, ne8 = (g.nedge + 7u) & ~7u;
-    BlockRole r;
-    r.edge = b < ne8;
-    r.idle = r.edge && b >= g.nedge;
-    const u32 fb = b - ne8;
-    r.index = r.edge ? b : range_first(g.nf, fb & 7u) + (fb >> 3);
-    // Which tiles the eight XCDs work on at one time (speed only; g.xmode, host policy xcd_mode()).  0: each XCD walks its
-    // own contiguous eighth of the band-ordered list -- eight places an eighth of the batch apart, a power-of-two distance
-    // on power-of-two frames.  1: whole bands dealt round-robin, so the XCDs work on eight CONSECUTIVE bands (16384^2:
-    // -10 % encode, -9 % decode; 64 x 4096^2: -1.5 ... -1.8 %; profiles/r03_ab_xcd.txt); what is left after the last
-    // multiple of eight bands is split contiguously as in mode 0.  (finish_grid() clears xmode when a frame's rows do not
-    // divide into whole bands.)
-    if (!r.edge && g.xmode == 1) {
-        const u32 x = fb & 7u, sq = fb >> 3;
-        if (sq < g.rr_own) {
-            const u32 round = fdiv(sq, g.fd_P);
-            r.index = (round * 8u + x) * g.P + (sq - round * g.P);
-        } else {
-            r.index = g.rr_tail0 + range_first(g.nf - g.rr_tail0, x) + (sq - g.rr_own);
-        }
-    }
-    return r;
-}
+// One block (= one wave) per tile, ONE launch per batch: the launch order and the block's role in it are hgi_tilewalk.h's.
+__device__ __forceinline__ BlockRole block_role(const TileGrid &g) { return walk_block_role(blockIdx.x, g); }
 
 #ifndef HGI_DEC_WAVES_PER_EU
 #define HGI_DEC_WAVES_PER_EU 8
@@ -1961,30 +1868,7 @@ inline u32 band_rows(const Frames &f, bool encode)
     return rows;
 }
 
-// Everything the kernels would otherwise derive per block from the launch's constants (and the divisions by them).
-inline void finish_grid(TileGrid &g)
-{
-    g.ex = g.full_x;
-    g.nf = g.nfast;
-    if (g.band < 1) g.band = 1;
-    g.tpf = g.ex * g.full_y;
-    g.P = g.band * g.ex;
-    g.nfull = (g.full_y / g.band) * g.P;
-    g.rem_rows = g.full_y % g.band;
-    g.fd_tpf = make_fastdiv(g.tpf);
-    g.fd_P = make_fastdiv(g.P);
-    g.fd_band = make_fastdiv(g.band);
-    g.fd_rem = make_fastdiv(g.rem_rows);
-    g.fd_ex = make_fastdiv(g.ex);
-    g.rr_own = g.rr_tail0 = 0;
-    if (g.xmode != 1 || g.rem_rows != 0 || g.P == 0 || g.nf == 0) {
-        g.xmode = 0;
-    } else {
-        const u32 nb8 = (g.nf / g.P) & ~7u;          // bands in whole rounds of eight
-        g.rr_own = (nb8 >> 3) * g.P;
-        g.rr_tail0 = nb8 * g.P;
-    }
-}
+// (finish_grid -- everything the kernels would otherwise derive per block from the launch's constants: hgi_tilewalk.h)
 
 // Dynamic LDS of a launch padded so that at most `waves` blocks fit a CU (160 KiB of LDS): a launch only a few rounds of
 // resident tiles deep pays a tile LIFETIME for filling and draining the chip, and the lifetime is resident tiles / rate

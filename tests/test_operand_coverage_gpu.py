@@ -9,7 +9,6 @@ what the forced-path children re-run on the knobs build), `variants` the pitched
 mapped kernels.  The oracle's grid and decode are computed once per (design, table, interpolator) and shared by both parts.
 Outputs with a pitch are written into sentinel-filled parents that are checked whole; inputs with a pitch are read out of
 parents of random bytes.  Expected bytes: the oracle.  Never the library under test."""
-import ctypes
 import functools
 import os
 import subprocess
@@ -19,9 +18,10 @@ import numpy as np
 import pytest
 
 import operand_designs as D
+from kernel_calls import (SENT, H, Plane, assert_same, call_list, ctxs, dev, injective_table, run_list, run_mapped, run_narrowed,  # noqa: F401
+                          run_pitched, run_recon, run_region, run_scaled, run_uniform, same_dev)
 
 pytestmark = pytest.mark.gpu
-SENT = 0xC3
 TABLES = D.tables()
 TABLES_PLUS = dict(TABLES, nonzero_origin=D.table_nonzero_origin())
 
@@ -57,241 +57,6 @@ def expected(design, tname, interp):
     _, levels, _, _ = DESIGNS[design]
     grid = O.encode(frame_of(design), levels, TABLES_PLUS[tname], interp)
     return grid, O.decode(grid, levels, interp)
-
-
-@pytest.fixture(scope="module")
-def H():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a device"
-    import rustyhgi_amd
-    from rustyhgi_amd import _ffi, _ffi_map, _ffi_recon
-    assert _ffi.lib() is not None and _ffi_recon.lib() is not None and _ffi_map.lib() is not None      # no fallback exists
-    return rustyhgi_amd
-
-
-@pytest.fixture(scope="module")
-def ctxs(H):
-    import torch
-    from rustyhgi_amd import _ffi
-    fused, levelwise = H.Context(0), H.Context(0)
-    levelwise.set_path(_ffi.PATH_LEVELWISE)
-    for c in (fused, levelwise):
-        c.set_stream(torch.cuda.current_stream().cuda_stream)
-    yield {"fused": fused, "levelwise": levelwise}
-    fused.close()
-    levelwise.close()
-
-
-def assert_same(a, b, what):
-    if a.shape != b.shape:
-        raise AssertionError("%s: shape %s, want %s" % (what, a.shape, b.shape))
-    if not (a == b).all():
-        bad = np.argwhere(a != b)
-        y, x = bad[0][-2:]
-        raise AssertionError("%s: %d mismatches, first at (x=%d, y=%d, x mod 16 = %d): got %d want %d"
-                             % (what, len(bad), x, y, x % 16, a[tuple(bad[0])], b[tuple(bad[0])]))
-
-
-def same_dev(got, want, what):
-    """Device tensors compared on the device; the host report only on a mismatch."""
-    import torch
-    if got.shape != want.shape or not torch.equal(got, want):
-        assert_same(got.cpu().numpy(), want.cpu().numpy(), what)
-
-
-class Plane:
-    """h rows of `row` bytes, `pitch` apart, `lead` bytes into a 1-D device buffer: an output plane is filled with the sentinel
-    and checked whole, an input plane holds random bytes around its rows.  `tail_w`: the row width of an input whose three
-    bytes behind the span must share a 4-KiB page with its last byte (include/hgi_recon.h, include/hgi_map.h)."""
-
-    def __init__(self, h, row, pitch, lead=0, random=False, seed=1, tail_w=None):
-        import torch
-        self.h, self.row, self.pitch, self.lead = h, row, pitch, lead
-        n = lead + (h - 1) * pitch + row + 64
-        if random:
-            gen = torch.Generator(device="cuda")
-            gen.manual_seed(seed)
-            self.buf = torch.randint(0, 256, (n,), dtype=torch.uint8, device="cuda", generator=gen)
-        else:
-            self.buf = torch.full((n,), SENT, dtype=torch.uint8, device="cuda")
-        if tail_w is not None and tail_w % 4:
-            end = self.ptr + (h - 1) * pitch + tail_w
-            if (end - 1) >> 12 != (end + 2) >> 12:
-                self.lead += 4
-            end = self.ptr + (h - 1) * pitch + tail_w
-            assert (end - 1) >> 12 == (end + 2) >> 12
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + self.lead
-
-    def rows(self, buf=None):
-        import torch
-        return torch.as_strided(self.buf if buf is None else buf, (self.h, self.row), (self.pitch, 1), self.lead)
-
-    def put(self, t):
-        self.rows().copy_(t)
-        return self
-
-    def intact(self, what):
-        c = self.buf.clone()
-        self.rows(c).fill_(SENT)
-        assert bool((c == SENT).all()), what + ": bytes outside the output rows written"
-
-
-def dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a if a.flags.writeable else a.copy()).cuda()
-
-
-def call_list(ctx, encode, ins, outs, shapes, levels, interp, lut=None):
-    from rustyhgi_amd import _ffi
-    L, n = _ffi.lib(), len(shapes)
-    pi, po = (ctypes.c_void_p * n)(*ins), (ctypes.c_void_p * n)(*outs)
-    ws, hs = (ctypes.c_uint32 * n)(*[w for w, h in shapes]), (ctypes.c_uint32 * n)(*[h for w, h in shapes])
-    if encode:
-        _ffi.check(L.hgi_encode_u8_list_dev(ctx.handle, pi, ws, hs, levels, interp, lut.ctypes.data, po, n))
-    else:
-        _ffi.check(L.hgi_decode_u8_list_dev(ctx.handle, pi, ws, hs, levels, interp, po, n))
-
-
-def injective_table(E, seed):
-    rng = np.random.default_rng(seed + 1000 * E)
-    if E == 2:
-        return rng.permutation(1 << 16)[:256].astype(np.uint16)
-    t = (rng.permutation(1 << 20)[:256].astype(np.uint32) << np.uint32(12)) | rng.integers(0, 4096, 256, dtype=np.uint32)
-    assert len(np.unique(t)) == 256
-    return t
-
-
-# ------------------------------------------------------------------------------------------------ entry points
-def run_uniform(ctxs, d_img, d_grid, d_dec, levels, interp, lut, what):
-    import torch
-    from rustyhgi_amd import _ffi
-    L = _ffi.lib()
-    h, w = d_img.shape
-    for path in ("fused", "levelwise"):
-        ctx = ctxs[path]
-        out = torch.full_like(d_img, 0xA5)
-        _ffi.check(L.hgi_encode_u8_dev(ctx.handle, d_img.data_ptr(), w, h, levels, interp, lut.ctypes.data, out.data_ptr(), 1, w * h))
-        same_dev(out, d_grid, "%s %s encode" % (what, path))
-        out.fill_(0x5A)
-        _ffi.check(L.hgi_decode_u8_dev(ctx.handle, d_grid.data_ptr(), w, h, levels, interp, out.data_ptr(), 1, w * h))
-        same_dev(out, d_dec, "%s %s decode" % (what, path))
-
-
-def run_pitched(ctx, d_img, d_grid, d_dec, levels, interp, lut, what, w=None, gaps=(61, 3), leads=(3, 16)):
-    """Encode and decode of the first `w` columns through pitches (w = None: the whole frame)."""
-    from rustyhgi_amd import _ffi
-    L = _ffi.lib()
-    h, full = d_img.shape
-    w = w or full
-    src = Plane(h, w, w + gaps[0], leads[0], random=True, seed=levels).put(d_img[:, :w])
-    dst = Plane(h, w, w + gaps[1], leads[1])
-    _ffi.check(L.hgi_encode_u8_pitched_dev(ctx.handle, src.ptr, src.pitch, w, h, levels, interp, lut.ctypes.data, dst.ptr, dst.pitch, 1,
-                                           h * src.pitch, h * dst.pitch))
-    same_dev(dst.rows(), d_grid, what + " pitched encode")
-    dst.intact(what + " pitched encode")
-    src = Plane(h, w, w + gaps[1], leads[1], random=True, seed=levels + 1).put(d_grid)
-    dst = Plane(h, w, w + gaps[0], leads[0])
-    _ffi.check(L.hgi_decode_u8_pitched_dev(ctx.handle, src.ptr, src.pitch, w, h, levels, interp, dst.ptr, dst.pitch, 1,
-                                           h * src.pitch, h * dst.pitch))
-    same_dev(dst.rows(), d_dec, what + " pitched decode")
-    dst.intact(what + " pitched decode")
-
-
-def run_list(ctx, oracle, img, d_img, d_grid, d_dec, levels, interp, lut, what):
-    """The frame and an odd-sized cut of it as one list of two."""
-    h, w = img.shape
-    h2, w2 = min(h, 131), min(w, 517)
-    cut = np.ascontiguousarray(img[:h2, :w2])
-    g2 = oracle.encode(cut, levels, lut, interp)
-    d2 = oracle.decode(g2, levels, interp)
-    shapes = [(w, h), (w2, h2)]
-    for encode, ins, wants in ((True, [d_img, dev(cut)], [d_grid, dev(g2)]), (False, [d_grid, dev(g2)], [d_dec, dev(d2)])):
-        outs = [Plane(1, ww * hh, ww * hh, lead) for (ww, hh), lead in zip(shapes, (7, 1))]
-        call_list(ctx, encode, [t.data_ptr() for t in ins], [o.ptr for o in outs], shapes, levels, interp, lut)
-        for k, (o, want) in enumerate(zip(outs, wants)):
-            name = "%s list %s frame %d" % (what, "encode" if encode else "decode", k)
-            same_dev(o.rows().reshape(want.shape), want, name)
-            o.intact(name)
-
-
-def run_recon(d_img, d_grid, d_dec, levels, interp, lut, what, w=None):
-    import torch
-    from rustyhgi_amd import _ffi_recon as R
-    h, full = d_img.shape
-    w = w or full
-    src = Plane(h, w, w + 16, 5, random=True, seed=levels, tail_w=w).put(d_img[:, :w])
-    grid, rec = Plane(h, w, w + 61, 1), Plane(h, w, w + 128, 16)
-    R.check(R.lib().hgi_recon_encode_u8_dev(torch.cuda.current_stream().cuda_stream or None, src.ptr, src.pitch, w, h, levels, interp,
-                                            lut.ctypes.data, grid.ptr, grid.pitch, rec.ptr, rec.pitch, 1, h * src.pitch,
-                                            h * grid.pitch, h * rec.pitch))
-    same_dev(grid.rows(), d_grid, what + " recon grid")
-    same_dev(rec.rows(), d_dec, what + " recon reconstruction")
-    grid.intact(what + " recon grid")
-    rec.intact(what + " recon reconstruction")
-
-
-def run_region(ctx, d_grid, d_dec, levels, interp, what):
-    """Two windows that cut the blocks at odd offsets; the second touches the right and bottom edges."""
-    from rustyhgi_amd import _ffi
-    h, w = d_grid.shape
-    x1, y1 = min(37, w - 1), min(21, h - 1)
-    rects = [(x1, y1, min(w - x1, 1001), min(h - y1, 333)), (w // 2 + 1, h // 2 + 3, w - w // 2 - 1, h - h // 2 - 3)]
-    for (x0, y0, rw, rh) in rects:
-        out = Plane(rh, rw, rw + 5, 3)
-        _ffi.check(_ffi.lib().hgi_decode_region_u8_dev(ctx.handle, d_grid.data_ptr(), w, h, levels, interp, x0, y0, rw, rh, out.ptr,
-                                                       out.pitch, 1, w * h, rh * out.pitch))
-        name = "%s region %r" % (what, (x0, y0, rw, rh))
-        same_dev(out.rows(), d_dec[y0:y0 + rh, x0:x0 + rw], name)
-        out.intact(name)
-
-
-def run_scaled(ctx, d_grid, d_dec, levels, interp, shift, what):
-    from rustyhgi_amd import _ffi
-    h, w = d_grid.shape
-    sw, sh = -(-w >> shift), -(-h >> shift)
-    out = Plane(sh, sw, sw + 13, 1)
-    _ffi.check(_ffi.lib().hgi_decode_scaled_u8_dev(ctx.handle, d_grid.data_ptr(), w, h, levels, interp, shift, out.ptr, out.pitch, 1,
-                                                   w * h, sh * out.pitch))
-    name = "%s scaled s=%d" % (what, shift)
-    same_dev(out.rows(), d_dec[::1 << shift, ::1 << shift], name)
-    out.intact(name)
-
-
-def run_mapped(d_grid, d_dec, levels, interp, E, what, w=None):
-    import torch
-    from rustyhgi_amd import _ffi_map as M
-    h, full = d_grid.shape
-    w = w or full
-    table = injective_table(E, levels)
-    d_table = dev(table.view({2: np.int16, 4: np.int32}[E]))
-    src = Plane(h, w, w + 3, 2, random=True, seed=levels + E, tail_w=w).put(d_grid[:, :w])
-    out = Plane(h, w * E, (w + 16) * E, 2 * E)
-    M.check(M.lib().hgi_map_decode_dev(torch.cuda.current_stream().cuda_stream or None, src.ptr, src.pitch, w, h, levels, interp,
-                                       d_table.data_ptr(), E, out.ptr, out.pitch, 1, h * src.pitch, h * out.pitch))
-    want = d_table[d_dec.long()]
-    got = out.rows().contiguous().view(d_table.dtype)
-    name = "%s mapped E=%d" % (what, E)
-    if not torch.equal(got, want):
-        assert_same(got.cpu().numpy(), want.cpu().numpy(), name)
-    out.intact(name)
-
-
-def run_narrowed(ctx, oracle, img, d_img, levels, interp, lut, what):
-    """The sub 1 and sub 2 designs at width - 1 and width - 2, as views of the same rows: widths 3 and 2 mod 4 take the checked
-    path in the core library and every `nvalid` class of the last chunk in the companions."""
-    h, w = img.shape
-    for k in (1, 2):
-        cut = np.ascontiguousarray(img[:, :w - k])
-        grid = oracle.encode(cut, levels, lut, interp)
-        d_g, d_d = dev(grid), dev(oracle.decode(grid, levels, interp))
-        name = "%s width-%d" % (what, k)
-        run_pitched(ctx, d_img, d_g, d_d, levels, interp, lut, name, w=w - k, gaps=(k, k), leads=(0, 0))
-        run_recon(d_img, d_g, d_d, levels, interp, lut, name, w=w - k)
-        run_mapped(d_g, d_d, levels, interp, 2 * k, name)
 
 
 @pytest.mark.parametrize("design,interp,part", CASES, ids=["%s-i%d-%s" % c for c in CASES])
