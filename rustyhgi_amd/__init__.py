@@ -4,7 +4,7 @@ Crate-root re-exports as in the reference's src/lib.rs:16-23:
     rustyhgi_amd.{Archive, Metadata, Decoder, Encoder}, rustyhgi_amd.interpolator, rustyhgi_amd.quantizator
 plus rustyhgi_amd.entropy (device-side byte histogram of the grid) and rustyhgi_amd.Planes (device
 buffers placed for MI355X's HBM regions, include/hgi.h hgi_planes_alloc) and rustyhgi_amd.mapping (the 256-entry tables of
-Decoder.decode_mapped, include/hgi_map.h).
+Decoder.decode_mapped, include/hgi_map.h, and the constants of Encoder.encode_typed, include/hgi_typed.h).
 All computation happens in libhgi_hip.so (hand-written HIP kernels); see include/hgi.h.
 """
 from . import entropy, interpolator, mapping, quantizator
@@ -12,8 +12,8 @@ from ._ffi import Context, HgiError, default_context
 from .archive import Archive, Metadata
 from .codec import Decoder, Encoder
 from .grid import Grid
-from .mapping import affine_table
+from .mapping import affine_inverse, affine_table
 from .planes import Planes
 
 __all__ = ["Encoder", "Decoder", "Grid", "Archive", "Metadata", "Context", "HgiError", "default_context", "interpolator",
-           "quantizator", "entropy", "Planes", "mapping", "affine_table"]
+           "quantizator", "entropy", "Planes", "mapping", "affine_table", "affine_inverse"]

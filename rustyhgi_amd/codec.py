@@ -478,6 +478,66 @@ class Encoder:
         _ffi_recon.check(st)
         return out, recon
 
+    def encode_typed(self, frames, scale=255.0, bias=0.0, out=None):
+        """Encode float frames where they lie: a (H, W) or (B, H, W) torch CUDA tensor of float16, bfloat16 or float32 -- a view
+        as for `encode_view`, strides counted in elements -- becomes the grids of the uint8 image `v = clamp(rint(x * scale +
+        bias), 0, 255)`, NaN -> 0: two separately rounded float32 operations, round half to even, denormals kept
+        (include/hgi_typed.h).  The defaults invert `affine_table(dtype)`; `rustyhgi_amd.affine_inverse(s, b)` gives the pair
+        that inverts `affine_table(dtype, s, b)`.  `out` may be a uint8 view (only its W-byte rows are written); without it a
+        packed uint8 tensor of the frames' shape is returned.  The result is bit for bit `encode_view` of that uint8 image, which
+        never reaches memory: ONE hgi_typed_encode_dev launch (libhgi_typed.so), asynchronous on the current stream -- E + 1
+        B/px instead of the E + 3 B/px of a conversion and an encode.  What that launch does not serve (HGI_EUNSUPPORTED: 0 or
+        more than 8 levels, offsets beyond 32 bits, 2-byte elements of an odd width whose last byte ends a 4-KiB page) is
+        composed from the torch conversion and `encode_view` on the same stream: the same bytes, not fused.  Validated
+        (ValueError) before any device call; empty inputs need no device."""
+        what = "encode_typed"
+        if not _is_torch(frames):
+            raise ValueError("%s: expected a float16, bfloat16 or float32 torch CUDA tensor" % what)
+        import torch
+        kinds = {torch.float16: (2, 0), torch.bfloat16: (2, 1), torch.float32: (4, 0)}      # dtype -> (elem_size, elem_kind)
+        if frames.dtype not in kinds:
+            raise ValueError("%s: expected a float16, bfloat16 or float32 tensor, not %s" % (what, frames.dtype))
+        esize, kind = kinds[frames.dtype]
+        lay = _typed_view_layout(frames, what, frames.dtype, esize)
+        with np.errstate(over="ignore"):
+            scale, bias = np.float32(scale), np.float32(bias)
+        if not (np.isfinite(scale) and np.isfinite(bias)):
+            raise ValueError("%s: `scale` and `bias` must be finite float32 values" % what)
+        if out is None:
+            if lay[1] * lay[2] * lay[3]:
+                _view_device(frames, what)
+            out = torch.empty(tuple(frames.shape), dtype=torch.uint8, device=frames.device)
+            olay = _view_layout(out, what)
+        else:
+            if not _is_torch(out):
+                raise ValueError("%s: `out` must be a torch tensor like the frames" % what)
+            olay = _view_layout(out, "%s (out)" % what)
+            if tuple(out.shape) != tuple(frames.shape):
+                raise ValueError("%s: `out` has shape %s, the frames %s" % (what, tuple(out.shape), tuple(frames.shape)))
+            if out.device != frames.device:
+                raise ValueError("%s: `out` lives on %s, the frames on %s" % (what, out.device, frames.device))
+        (src, b, h, w, sp, sfs, ispan), (dst, _, _, _, dp, dfs, gspan) = lay, olay
+        if b * h * w and src < dst + (b - 1) * dfs + gspan and dst < src + (b - 1) * sfs + ispan:
+            raise ValueError("%s: `out` shares memory with the frames (byte spans, tested conservatively)" % what)
+        if b * h * w == 0:
+            return out
+        _view_device(frames, what)
+        from . import _ffi_typed
+        dev = frames.device.index if frames.device.index is not None else torch.cuda.current_device()
+        if self._ctx is not None and self._ctx.device != dev:      # both routes judge the Encoder's context alike (_bind_ctx)
+            raise ValueError("tensor lives on cuda:%d but the context was created for cuda:%d" % (dev, self._ctx.device))
+        with torch.cuda.device(dev):
+            st = _ffi_typed.lib().hgi_typed_encode_dev(
+                _ffi._vp(torch.cuda.current_stream(dev).cuda_stream or 0), src, sp, esize, kind, float(scale), float(bias), w, h,
+                self.scale_level, self._interp, self._lut.ctypes.data, dst, dp, b, sfs, dfs)
+        if st == _ffi.EUNSUPPORTED:      # not served by the one launch: the same bytes from a conversion and an encode
+            t = torch.add(torch.mul(frames.to(torch.float32), float(scale)), float(bias))      # two roundings, as the launch does
+            px = torch.where(torch.isnan(t), torch.zeros_like(t), t).round().clamp(0, 255).to(torch.uint8)
+            self.encode_view(px, out=out)
+            return out
+        _ffi_typed.check(st)
+        return out
+
     def encode_list(self, images, out=None):
         """A list of (h_i, w_i) uint8 frames of any shapes -> the list of their residual planes.  CUDA tensors (one device,
         contiguous): ONE hgi_encode_u8_list_dev call, asynchronous on the current stream, the outputs (h_i, w_i) views into one

@@ -1,4 +1,5 @@
-"""Tables of `Decoder.decode_mapped` (include/hgi_map.h): 256 output elements, one per value of a decoded pixel.
+"""Tables of `Decoder.decode_mapped` (include/hgi_map.h): 256 output elements, one per value of a decoded pixel -- and the
+constants of `Encoder.encode_typed` (include/hgi_typed.h) that take such frames back to pixels.
 
 The codec moves the table's bits and does no float arithmetic, so whatever conversion a pipeline wants -- x / 255, mean / std
 normalisation, gamma -- is computed here, once, on the host or by torch, and never repeated by the library.
@@ -25,3 +26,11 @@ def affine_table(dtype, scale=1.0 / 255.0, bias=0.0, device=None):
         return tab
     import torch
     return torch.from_numpy(tab).to(device)
+
+
+def affine_inverse(scale=1.0 / 255.0, bias=0.0):
+    """The `(scale, bias)` of `Encoder.encode_typed` that invert `affine_table(dtype, scale, bias)`: float32
+    `(1 / scale, -bias / scale)`, so that `x * (1 / scale) + (-bias / scale)` rounds back to the pixel v that the table mapped
+    to x = v * scale + bias.  Both quotients are float32 divisions of the float32 arguments."""
+    s, b = np.float32(scale), np.float32(bias)
+    return np.float32(1) / s, -b / s
