@@ -110,8 +110,9 @@ def tile_classes(w, h, th):
 
 
 # ----------------------------------------------------------------------------- the out-of-image rule, restated
-def _lattice(img, step, mutant):
-    """oracle/hgi_numpy.py:_corner_lattice with the coordinates of every corner at hand: (values, cx, cy, altered)."""
+def _lattice(img, step, mutant, fill=MUTANT_FILL):
+    """oracle/hgi_numpy.py:_corner_lattice with the coordinates of every corner at hand: (values, altered).  `fill`: what the
+    mutants `right`, `below` and `corner` read outside the image."""
     h, w = img.shape
     ny, nx = -(-h // step) + 1, -(-w // step) + 1
     cy, cx = np.arange(ny)[:, None] * step, np.arange(nx)[None, :] * step
@@ -122,11 +123,11 @@ def _lattice(img, step, mutant):
     if mutant is None:
         return lat, None
     if mutant == "right":
-        hit, val = (cx >= w) & (cy >= 0), MUTANT_FILL
+        hit, val = (cx >= w) & (cy >= 0), fill
     elif mutant == "below":
-        hit, val = (cy >= h) & (cx >= 0), MUTANT_FILL
+        hit, val = (cy >= h) & (cx >= 0), fill
     elif mutant == "corner":
-        hit, val = (cx >= w) & (cy >= h), MUTANT_FILL
+        hit, val = (cx >= w) & (cy >= h), fill
     elif mutant == "last_col":
         hit, val = (cx == w - 1) & inside, 0
     elif mutant == "last_row":
@@ -137,8 +138,8 @@ def _lattice(img, step, mutant):
     return lat, hit
 
 
-def _prediction(img, step, interp, mutant):
-    lat, _ = _lattice(img, step, mutant)
+def _prediction(img, step, interp, mutant, fill=MUTANT_FILL):
+    lat, _ = _lattice(img, step, mutant, fill)
     lt, rt, lb, rb = lat[:-1, :-1], lat[1:, :-1], lat[:-1, 1:], lat[1:, 1:]
     if interp == LEFTTOP:
         return lt.astype(np.uint8)
@@ -146,7 +147,7 @@ def _prediction(img, step, interp, mutant):
     return ((avg(lt, lb) + avg(rb, rt) + avg(rt, lt) + avg(rb, lb)) >> 2).astype(np.uint8)
 
 
-def encode_oob(img, levels, lut, interp=CROSSED, mutant=None):
+def encode_oob(img, levels, lut, interp=CROSSED, mutant=None, fill=MUTANT_FILL):
     """oracle/hgi_numpy.py:encode on the lattice above."""
     img = np.ascontiguousarray(img, np.uint8)
     lut = np.asarray(lut, np.uint8)
@@ -156,7 +157,7 @@ def encode_oob(img, levels, lut, interp=CROSSED, mutant=None):
     for level in range(levels):
         step = 1 << (levels - level)
         sub = step >> 1
-        pred = _prediction(rec, step, interp, mutant)
+        pred = _prediction(rec, step, interp, mutant, fill)
         for rv, gv in zip(N._level_views(rec, sub), N._level_views(grid, sub)):
             p = pred[: rv.shape[0], : rv.shape[1]]
             a = rv.copy()

@@ -4,9 +4,12 @@ Outputs with a pitch are written into sentinel-filled parents that are checked w
 parents of random bytes.  Device tensors are compared on the device; the host report is made only on a mismatch."""
 import bisect
 import ctypes
+import functools
 
 import numpy as np
 import pytest
+
+import typed_reference as TR
 
 SENT = 0xC3
 PAGE = 4096
@@ -17,8 +20,9 @@ def H():
     import torch
     assert torch.cuda.is_available(), "GPU tests need a device"
     import rustyhgi_amd
-    from rustyhgi_amd import _ffi, _ffi_map, _ffi_recon
+    from rustyhgi_amd import _ffi, _ffi_map, _ffi_recon, _ffi_typed
     assert _ffi.lib() is not None and _ffi_recon.lib() is not None and _ffi_map.lib() is not None      # no fallback exists
+    assert _ffi_typed.lib() is not None
     return rustyhgi_amd
 
 
@@ -54,10 +58,11 @@ def same_dev(got, want, what):
 
 class Plane:
     """h rows of `row` bytes, `pitch` apart, `lead` bytes into a 1-D device buffer: an output plane is filled with the sentinel
-    and checked whole, an input plane holds random bytes around its rows.  `tail_w`: the row width of an input whose three
-    bytes behind the span must share a 4-KiB page with its last byte (include/hgi_recon.h, include/hgi_map.h)."""
+    and checked whole, an input plane holds random bytes around its rows.  `tail_w`: the row width of an input whose `tail_n`
+    bytes behind the span must share a 4-KiB page with its last byte (three: include/hgi_recon.h, include/hgi_map.h; two, for
+    2-byte elements of an odd width: include/hgi_typed.h)."""
 
-    def __init__(self, h, row, pitch, lead=0, random=False, seed=1, tail_w=None):
+    def __init__(self, h, row, pitch, lead=0, random=False, seed=1, tail_w=None, tail_n=3):
         import torch
         self.h, self.row, self.pitch, self.lead = h, row, pitch, lead
         n = lead + (h - 1) * pitch + row + 64
@@ -69,10 +74,10 @@ class Plane:
             self.buf = torch.full((n,), SENT, dtype=torch.uint8, device="cuda")
         if tail_w is not None and tail_w % 4:
             end = self.ptr + (h - 1) * pitch + tail_w
-            if (end - 1) >> 12 != (end + 2) >> 12:
+            if (end - 1) >> 12 != (end + tail_n - 1) >> 12:
                 self.lead += 4
             end = self.ptr + (h - 1) * pitch + tail_w
-            assert (end - 1) >> 12 == (end + 2) >> 12
+            assert (end - 1) >> 12 == (end + tail_n - 1) >> 12
 
     @property
     def ptr(self):
@@ -233,9 +238,71 @@ def run_mapped(d_grid, d_dec, levels, interp, E, what, w=None):
     out.intact(name)
 
 
-def run_narrowed(ctx, oracle, img, d_img, levels, interp, lut, what):
+# typed encode: element size -> kinds, kind -> elem_kind of the ABI; the (scale, bias) pairs of the coverage suites.  Under
+# (1, 37.25) the element 0.0 means pixel 37, under (-3.5, 300) pixel 255; bfloat16 reaches 224 of the 256 values under the
+# latter (tests/test_typed_coverage.py), so it runs under the former alone.
+F16, BF16, F32 = "float16", "bfloat16", "float32"
+EKIND = {F16: 0, BF16: 1, F32: 0}
+ESIZE = {F16: 2, BF16: 2, F32: 4}
+PAIR_A, PAIR_B = (1.0, 37.25), (-3.5, 300.0)
+
+
+def typed_choice(E, n):
+    """(kind, pair) of the n-th typed frame of E-byte elements: 2-byte kinds alternate float16 / bfloat16, the pairs alternate
+    where the kind allows both."""
+    if E == 4:
+        return F32, (PAIR_A, PAIR_B)[n % 2]
+    return (F16, (PAIR_A, PAIR_B)[(n // 2) % 2]) if n % 2 == 0 else (BF16, PAIR_A)
+
+
+TYPED_CHOICES = tuple(sorted({typed_choice(E, n) for E in (2, 4) for n in range(4)}))
+
+
+@functools.lru_cache(maxsize=None)
+def bank(kind, pair):
+    """tests/typed_reference.py:preimages, read-only (its condition is asserted in tests/test_typed_coverage.py)."""
+    b = TR.preimages(kind, *pair)
+    b.setflags(write=False)
+    return b
+
+
+@functools.lru_cache(maxsize=None)
+def bank_dev(kind, pair):
+    return dev(bank(kind, pair).view({2: np.int16, 4: np.int32}[ESIZE[kind]]))
+
+
+def lift_dev(d_img_u8, kind, pair, salt=0):
+    """The design lifted on the device (indexing of the uploaded bank: plumbing): element bit patterns, int16 / int32."""
+    return TR.lift(d_img_u8, bank_dev(kind, pair), salt)
+
+
+def run_typed(d_img_u8, d_grid, levels, interp, lut, E, kind, pair, what, w=None, lifted=None):
+    """hgi_typed_encode_dev on the first `w` columns of the design lifted to `kind` elements under the (scale, bias) `pair`
+    (`lifted`: the whole design lifted already -- it does not depend on the table).  The frame sits in a parent of random
+    bytes, so the gap elements are arbitrary bit patterns, NaN and infinity included."""
+    import torch
+    from rustyhgi_amd import _ffi_typed as T
+    assert ESIZE[kind] == E
+    h, full = d_img_u8.shape
+    w = w or full
+    if lifted is None:
+        lifted = lift_dev(d_img_u8, kind, pair)
+    src = Plane(h, w * E, (w + 3) * E, 3 * E, random=True, seed=levels + E, tail_w=w * E if E == 2 and w % 2 else None, tail_n=2)
+    src.put(lifted[:, :w].contiguous().view(torch.uint8))
+    before = src.buf.clone()
+    dst = Plane(h, w, w + 61, 5)
+    T.check(T.lib().hgi_typed_encode_dev(torch.cuda.current_stream().cuda_stream or None, src.ptr, src.pitch, E, EKIND[kind], pair[0], pair[1],
+                                         w, h, levels, interp, lut.ctypes.data, dst.ptr, dst.pitch, 1, h * src.pitch, h * dst.pitch))
+    name = "%s typed %s x %r + %r" % (what, kind, pair[0], pair[1])
+    same_dev(dst.rows(), d_grid, name)
+    dst.intact(name)
+    assert torch.equal(src.buf, before), name + ": the image parent was modified"
+
+
+def run_narrowed(ctx, oracle, img, d_img, levels, interp, lut, what, typed=None):
     """The sub 1 and sub 2 designs at width - 1 and width - 2, as views of the same rows: widths 3 and 2 mod 4 take the checked
-    path in the core library and every `nvalid` class of the last chunk in the companions."""
+    path in the core library and every `nvalid` class of the last chunk in the companions.  `typed`: {E: (kind, pair, lifted
+    design)} -- the typed call at both widths and element sizes, so also odd widths of 2-byte elements."""
     h, w = img.shape
     for k in (1, 2):
         cut = np.ascontiguousarray(img[:, :w - k])
@@ -245,6 +312,8 @@ def run_narrowed(ctx, oracle, img, d_img, levels, interp, lut, what):
         run_pitched(ctx, d_img, d_g, d_d, levels, interp, lut, name, w=w - k, gaps=(k, k), leads=(0, 0))
         run_recon(d_img, d_g, d_d, levels, interp, lut, name, w=w - k)
         run_mapped(d_g, d_d, levels, interp, 2 * k, name)
+        for E, (kind, pair, lifted) in sorted((typed or {}).items()):
+            run_typed(d_img, d_g, levels, interp, lut, E, kind, pair, name, w=w - k, lifted=lifted)
 
 
 class Pool:
@@ -255,21 +324,28 @@ class Pool:
     def __init__(self, output, seed=0):
         self.output, self.seed, self.n, self.items, self.offs = output, seed, 64, [], []
 
-    def add(self, data, pitch=None, stride=None, lead=0, align=1, end_mod=None, tail_safe=False, tag=None):
+    def add(self, data, pitch=None, stride=None, lead=0, align=1, end_mod=None, tail_safe=False, tag=None, phase=None):
         """data: (frames, h, row bytes).  Returns the offset of frame 0's first byte.  end_mod: the batch ends at this offset
         of its page; tail_safe: the three bytes behind the batch lie in the page of its last byte (rows that are not a multiple
-        of 4 bytes: the contract of the companion calls)."""
+        of 4 bytes: the contract of the companion calls; it serves the two tail bytes of typed encode too, whose last allowed
+        placement is end_mod = PAGE - 2: the tail records are then the page's last two bytes).  phase: the offset modulo 16 (a
+        multiple of `align`), kept by tail_safe; an end_mod moves it by a multiple of `align`."""
         frames, h, row = data.shape
         pitch = row if pitch is None else pitch
         stride = h * pitch if stride is None else stride
         assert pitch >= row and (frames == 1 or stride >= (h - 1) * pitch + row)
         span = (frames - 1) * stride + (h - 1) * pitch + row
         off = -(-(self.n + lead) // align) * align
+        if phase is not None:
+            assert phase % align == 0 and 16 % align == 0
+            off += (phase - off) % 16
         if end_mod is not None:
+            assert (end_mod - span) % align == 0
             off += (end_mod - (off + span)) % PAGE
         if tail_safe:
             while (off + span) % PAGE in (0, PAGE - 2, PAGE - 1):
-                off += 4
+                off += 4 if phase is None else 16
+        assert off % align == 0
         self.items.append((off, span, data, pitch, stride, tag))
         self.offs.append(off)
         self.n = off + span + 7

@@ -9,6 +9,8 @@ sentinel-filled device buffer, at their own leads and pitches, and the buffer is
 device (the host is asked only on a mismatch); all inputs lie in one buffer of nonzero random bytes -- pixels are noise in
 [8, 255], so no byte a kernel may wrongly read is 0, the out-of-image value -- which must come back unchanged.  The oracle's
 grids and decodes are computed once per (set, levels, table, interpolator) and shared by the families, which run back to back.
+The family `typed` feeds hgi_typed_encode_dev the same pixels lifted to float16 / bfloat16 / float32 elements
+(tests/typed_reference.py:preimages) under (scale, bias) pairs for which the element 0.0 is not pixel 0.
 Expected bytes: the oracle.  Never the library under test."""
 import functools
 import os
@@ -19,10 +21,11 @@ import numpy as np
 import pytest
 
 import geometry_designs as G
-from kernel_calls import H, Pool, call_list, ctxs, injective_table  # noqa: F401
+import typed_reference as TR
+from kernel_calls import EKIND, PAGE, H, Pool, bank, call_list, ctxs, injective_table, typed_choice  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-FAMILIES = ("uniform", "pitched", "list", "recon", "mapped", "scaled", "region")
+FAMILIES = ("uniform", "pitched", "list", "recon", "mapped", "typed", "scaled", "region")
 
 
 def tables():
@@ -43,8 +46,8 @@ def _keys():
     return keys
 
 
-# reconstruction and mapped decode take up to eight levels: their contract
-CASES = [(fam,) + key for key in _keys() for fam in FAMILIES if not (fam in ("recon", "mapped") and key[1] > 8)]
+# reconstruction, mapped decode and typed encode take up to eight levels: their contract
+CASES = [(fam,) + key for key in _keys() for fam in FAMILIES if not (fam in ("recon", "mapped", "typed") and key[1] > 8)]
 
 
 @functools.lru_cache(maxsize=4)
@@ -173,6 +176,62 @@ def fam_mapped(ctxs, E, levels, interp, lut, what):
     return n
 
 
+@functools.lru_cache(maxsize=4)
+def lifted_set(setname, esz):
+    """[(kind, (scale, bias), (2, h, w * esz) bytes)] for every shape of the set: its content lifted to elements that convert to
+    exactly that content (tests/typed_reference.py:preimages; the condition is asserted in tests/test_typed_coverage.py).  Kind and
+    pair go by the shape's index: float16 / bfloat16 alternate, and so do the pairs where the kind allows both.  Once per (set,
+    element size): the frames depend on neither the depth nor the table."""
+    out = []
+    for k, (w, h) in enumerate(G.shape_set(setname)):
+        kind, pair = typed_choice(esz, k)
+        frames = TR.lift(G.content(w, h, batch=2), bank(kind, pair), k)
+        out.append((kind, pair, np.ascontiguousarray(frames).view(np.uint8).reshape(2, h, w * esz)))
+    return out
+
+
+def typed_cases(E, lifted, esz, levels, interp, lut, what, seed):
+    """One pool of inputs, one of outputs and the calls of hgi_typed_encode_dev for the shapes of E (batch 2).  By shape index:
+    the image gap cycles through 1, 3, 16 and 61 elements and the first row's address through every multiple of the element
+    size below 16, so that row starts take every 16-byte phase; frame strides lie above the span on both sides; the grid is
+    placed as fam_pitched places it.  2-byte elements of an odd width read two bytes behind the last frame's span
+    (include/hgi_typed.h): they are placed tail_safe, every eighth of them with its span ending 2 bytes before a page end, the
+    last placement the contract serves."""
+    import torch
+    from rustyhgi_amd import _ffi_typed as T
+    stream = torch.cuda.current_stream().cuda_stream or None
+    inp, out, calls, n_odd = Pool(False, seed), Pool(True), [], 0
+    for k, ((w, h, img, grid, dec), (kind, pair, frames)) in enumerate(zip(E, lifted)):
+        assert frames.shape == (2, h, w * esz)
+        pi, pg = (w + (1, 3, 16, 61)[k % 4]) * esz, _odd(w + 3)
+        si, sg = h * pi + 2 * esz, h * pg + 1
+        place = {}
+        if esz == 2 and w % 2:
+            n_odd += 1
+            place = dict(end_mod=PAGE - 2) if n_odd % 8 == 0 else dict(tail_safe=True)
+        tag = "%d x %d typed %s x %r + %r" % (w, h, kind, pair[0], pair[1])
+        calls.append((w, h, EKIND[kind], pair, pi, pg, si, sg, inp.add(frames, pi, si, align=esz, phase=esz * (k % (16 // esz)), **place),
+                      out.add(grid, pg, sg, lead=17, tag=tag)))
+    inp.upload(), out.upload()
+    for w, h, ekind, pair, pi, pg, si, sg, i_img, o in calls:
+        T.check(T.lib().hgi_typed_encode_dev(stream, inp.ptr + i_img, pi, esz, ekind, pair[0], pair[1], w, h, levels, interp, lut.ctypes.data,
+                                             out.ptr + o, pg, 2, si, sg))
+    return inp, out, len(calls)
+
+
+def fam_typed(ctxs, E, levels, interp, lut, what, setname):
+    """hgi_typed_encode_dev with 2- and 4-byte elements (see typed_cases): the shapes' content lifted to float16 / bfloat16 /
+    float32 frames under (scale, bias) pairs for which the element 0.0 is NOT pixel 0 -- 37 under (1, 37.25), 255 under
+    (-3.5, 300) -- so that a load outside the image that reads an element 0.0 instead of writing pixel 0 changes the grid
+    (tests/test_typed_coverage.py shows on which shapes).  The frames of one row are in: their pitch counts as the row."""
+    n = 0
+    for esz in (2, 4):
+        inp, out, calls = typed_cases(E, lifted_set(setname, esz), esz, levels, interp, lut, what, levels + 700 + esz)
+        out.check(what), inp.check(what)
+        n += calls
+    return n
+
+
 def fam_scaled(ctxs, E, levels, interp, lut, what, key):
     """hgi_decode_scaled_u8_dev at s = 1 and 2.  The sweep is over OUTPUT remainders: for an output shape (sw, sh) of R1 the
     source frames are ((sw << s) - t, (sh << s) - t) with t = 0 and t = 2^s - 1.  The call reads the stride-2^s lattice of the
@@ -245,10 +304,38 @@ def test_every_remainder_through_every_entry_point(H, ctxs, family, setname, lev
     if family == "scaled":
         E = expected(*key) if setname == "D" else None
         n = fam_scaled(ctxs, E, levels, interp, lut, what, key)
+    elif family == "typed":
+        n = fam_typed(ctxs, expected(*key), levels, interp, lut, what, setname)
     else:
         n = RUN[family](ctxs, expected(*key), levels, interp, lut, what)
     torch.cuda.synchronize()
     print("%s: %d calls" % (what, n))
+
+
+def test_typed_family_notices_one_wrong_pixel(H, oracle):
+    """The whole-buffer comparison of the typed family on a 131 x 66 case (4 levels, the identity table, both element sizes) in
+    which ONE element of the input -- the last of the second frame -- is a preimage of another pixel value: Pool.check raises
+    and names the case.  The same case untouched passes."""
+    import torch
+    w, h, levels = 131, 66, 4
+    img = G.content(w, h, batch=2)
+    lut = np.ascontiguousarray(TABLES["identity"])
+    grid = np.stack([oracle.encode(img[f], levels, lut, 1) for f in range(2)])
+    E = [(w, h, img, grid, None)]
+    for esz in (2, 4):
+        kind, pair = typed_choice(esz, 1)
+        good = np.ascontiguousarray(TR.lift(img, bank(kind, pair), 1))
+        inp, out, _ = typed_cases(E, [(kind, pair, good.view(np.uint8).reshape(2, h, w * esz))], esz, levels, 1, lut, "self-check", 770)
+        out.check("self-check"), inp.check("self-check")
+        bad = good.copy()
+        other = (int(img[1, -1, -1]) + 100) % 256
+        bad[1, -1, -1] = bank(kind, pair)[other, 0]
+        assert TR.quantize(TR.elements(kind, bad[1, -1, -1:]), *pair)[0] == other != img[1, -1, -1]
+        inp, out, _ = typed_cases(E, [(kind, pair, bad.view(np.uint8).reshape(2, h, w * esz))], esz, levels, 1, lut, "self-check", 771)
+        with pytest.raises(AssertionError, match=r"self-check 131 x 66 typed %s .*first in frame 1 at \(x=130, y=65" % kind):
+            out.check("self-check")
+        inp.check("self-check")
+    torch.cuda.synchronize()
 
 
 def test_scaled_sources_are_what_the_full_decode_subsamples(oracle):

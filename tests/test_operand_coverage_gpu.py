@@ -5,8 +5,9 @@ quantizer step, the predictor designs every corner quadruple over the edge value
 confined to one lane at p = 255 or to one carry fails here and nowhere else in the suite.
 
 One test case is (design, interpolator, part): `uniform` runs the *_dev calls on a fused and on a level-wise context (and is
-what the forced-path children re-run on the knobs build), `variants` the pitched, list, reconstruction, region, scaled and
-mapped kernels.  The oracle's grid and decode are computed once per (design, table, interpolator) and shared by both parts.
+what the forced-path children re-run on the knobs build), `variants` the pitched, list, reconstruction, region, scaled,
+mapped and typed kernels (typed encode takes the design lifted to float16 / bfloat16 / float32 elements whose conversion is
+exactly the design: tests/typed_reference.py:preimages).  The oracle's grid and decode are computed once per (design, table, interpolator) and shared by both parts.
 Outputs with a pitch are written into sentinel-filled parents that are checked whole; inputs with a pitch are read out of
 parents of random bytes.  Expected bytes: the oracle.  Never the library under test."""
 import functools
@@ -18,8 +19,8 @@ import numpy as np
 import pytest
 
 import operand_designs as D
-from kernel_calls import (SENT, H, Plane, assert_same, call_list, ctxs, dev, injective_table, run_list, run_mapped, run_narrowed,  # noqa: F401
-                          run_pitched, run_recon, run_region, run_scaled, run_uniform, same_dev)
+from kernel_calls import (SENT, H, Plane, assert_same, call_list, ctxs, dev, injective_table, lift_dev, run_list, run_mapped,  # noqa: F401
+                          run_narrowed, run_pitched, run_recon, run_region, run_scaled, run_typed, run_uniform, same_dev, typed_choice)
 
 pytestmark = pytest.mark.gpu
 TABLES = D.tables()
@@ -44,6 +45,22 @@ DESIGNS = _designs()
 CASES = [(d, i, part) for d in DESIGNS for i in (1, 0) for part in ("uniform", "variants")]
 
 
+def narrowed(design, tname):
+    return design.startswith(("q1_", "q2_")) and tname in ("linear2", "identity")
+
+
+def typed_calls(design, interp):
+    """The typed calls of a design's `variants` part: [(table name, E, kind, (scale, bias), also narrowed)].  Typed encode takes
+    up to eight levels (its contract).  Kind and pair go by the design's place in DESIGNS and the interpolator, not by the
+    table, so that the design is lifted once per element size.  tests/test_typed_coverage.py counts the kernel instantiations
+    these calls reach."""
+    _, levels, tnames, _ = DESIGNS[design]
+    if levels > 8:
+        return []
+    n = list(DESIGNS).index(design) + interp
+    return [(tname, E) + typed_choice(E, n) + (narrowed(design, tname),) for tname in tnames for E in (2, 4)]
+
+
 def frame_of(design):
     f = DESIGNS[design][0]
     return D.pred_frame(f) if f in D.PRED_FRAMES else D.quant_frame(f)
@@ -64,12 +81,18 @@ def test_design_through_every_entry_point(H, ctxs, oracle, design, interp, part)
     """Every table of the design, one interpolator: `uniform` -- hgi_encode_u8_dev / hgi_decode_u8_dev on a fused and on a
     level-wise context; `variants` -- pitched, frame list, encode with reconstruction (grid and reconstruction), region (two
     windows at odd offsets), scaled at s = 1 and 2 where a targeted level survives the shift, mapped decode with E = 2 and 4
-    and an injective table (reconstruction and mapping up to eight levels: their contract); the sub 1 and sub 2 designs also at
-    width - 1 and width - 2 under two tables.  All against the oracle, bit for bit."""
+    and an injective table, typed encode with E = 2 and 4 (reconstruction, mapping and typed encode up to eight levels: their
+    contract); the sub 1 and sub 2 designs also at width - 1 and width - 2 under two tables.  All against the oracle, bit for bit."""
     _, levels, tnames, subs = DESIGNS[design]
     img = frame_of(design)
     d_img = dev(img)
     fused = ctxs["fused"]
+    typed = {}
+    if part == "variants":
+        calls = typed_calls(design, interp)
+        # lifted once per (design, E): the frame does not depend on the table
+        typed = {E: (kind, pair, lift_dev(d_img, kind, pair, salt=levels)) for _, E, kind, pair, _ in calls[:2]}
+        assert all(typed[E][:2] == (kind, pair) for _, E, kind, pair, _ in calls)
     for tname in tnames:
         lut = np.ascontiguousarray(TABLES_PLUS[tname])
         grid, dec = expected(design, tname, interp)
@@ -88,8 +111,10 @@ def test_design_through_every_entry_point(H, ctxs, oracle, design, interp, part)
             run_recon(d_img, d_grid, d_dec, levels, interp, lut, what)
             for E in (2, 4):
                 run_mapped(d_grid, d_dec, levels, interp, E, what)
-        if design.startswith(("q1_", "q2_")) and tname in ("linear2", "identity"):
-            run_narrowed(fused, oracle, img, d_img, levels, interp, lut, what)
+            for E, (kind, pair, lifted) in sorted(typed.items()):
+                run_typed(d_img, d_grid, levels, interp, lut, E, kind, pair, what, lifted=lifted)
+        if narrowed(design, tname):
+            run_narrowed(fused, oracle, img, d_img, levels, interp, lut, what, typed=typed)
 
 
 # ------------------------------------------------------------------------------------ forced paths, knobs build

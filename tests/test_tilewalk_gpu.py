@@ -7,7 +7,10 @@ hgi_encode_u8_dev / hgi_decode_u8_dev at three levels, against the oracle.  Ever
 is checked whole: a tile that no block reaches leaves sentinels behind, a tile reached twice by different frames' blocks
 shows as wrong bytes.  In-process they run on the release library with its own policy (bands of 4 or 8 rows, round-robin
 dealing where a launch has eight whole bands); children on the knobs build force 16-row tiles, bands of 1 ... 4 rows, both
-XCD dealings and the backwards walk, which the release library reaches on wide or huge frames only."""
+XCD dealings and the backwards walk, which the release library reaches on wide or huge frames only.
+
+hgi_typed_encode_dev takes its block -> tile map from the pitched plan (rustyhgi_amd/typed/hgi_typed_plan.h): the same cases go
+through it in-process, with a pitch on both sides.  Its library has no knobs build, so it has no children."""
 import functools
 import os
 import subprocess
@@ -17,7 +20,8 @@ import numpy as np
 import pytest
 
 import geometry_designs as G
-from kernel_calls import H, Pool, ctxs  # noqa: F401
+import typed_reference as TR
+from kernel_calls import EKIND, H, Pool, bank, ctxs, typed_choice  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 LEVELS = 3
@@ -60,6 +64,36 @@ def test_walk_cases_against_the_oracle(H, ctxs, ex, tname):
         _ffi.check(L.hgi_encode_u8_dev(hd, inp.ptr + i_img, w, h, LEVELS, 1, lut.ctypes.data, out.ptr + o_enc, b, w * h))
         _ffi.check(L.hgi_decode_u8_dev(hd, inp.ptr + i_grid, w, h, LEVELS, 1, out.ptr + o_dec, b, w * h))
     what = "walk cases ex %d %s" % (ex, tname)
+    out.check(what), inp.check(what)
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("ex", (1, 2, 3))
+def test_walk_cases_through_typed_encode(H, ex):
+    """The WALK cases with `ex` interior tile columns through hgi_typed_encode_dev at three levels, Crossed: element size
+    alternating 2 / 4 by case, the table linear_lut(2) / identity by pairs of cases, the frames lifted to elements that convert
+    to exactly the cases' pixels (tests/typed_reference.py:preimages) and read through a pitch, the grids written through one;
+    one sentinel-filled buffer compared whole, the inputs unchanged."""
+    import torch
+    from rustyhgi_amd import _ffi_typed as T
+    stream = torch.cuda.current_stream().cuda_stream or None
+    inp, out, calls = Pool(False, 810 + ex), Pool(True), []
+    for k, (w, h, b) in enumerate(c for c in G.walk_cases() if c[0] // 128 == ex):
+        esz, tname = (2, 4)[k % 2], ("linear2", "identity")[(k // 2) % 2]
+        kind, pair = typed_choice(esz, k // 2)
+        img, grid, _ = frames_of(w, h, tname)
+        frames = np.ascontiguousarray(TR.lift(img[:b], bank(kind, pair), k)).view(np.uint8).reshape(b, h, w * esz)
+        pi, pg = (w + (1, 3, 16, 61)[k % 4]) * esz, (w + 3) | 1
+        si, sg = h * pi + 2 * esz, h * pg + 1
+        calls.append((w, h, b, esz, EKIND[kind], pair, table(tname), pi, pg, si, sg,
+                      inp.add(frames, pi, si, align=esz, phase=esz * (k % (16 // esz)), tail_safe=esz == 2 and w % 2 == 1),
+                      out.add(grid[:b], pg, sg, lead=17, tag="%d x %d batch %d typed %s %s" % (w, h, b, kind, tname))))
+    assert len(calls) == 200
+    inp.upload(), out.upload()
+    for w, h, b, esz, ekind, pair, lut, pi, pg, si, sg, i_img, o in calls:
+        T.check(T.lib().hgi_typed_encode_dev(stream, inp.ptr + i_img, pi, esz, ekind, pair[0], pair[1], w, h, LEVELS, 1, lut.ctypes.data,
+                                             out.ptr + o, pg, b, si, sg))
+    what = "typed walk cases ex %d" % ex
     out.check(what), inp.check(what)
     torch.cuda.synchronize()
 
