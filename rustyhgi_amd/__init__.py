@@ -5,6 +5,7 @@ Crate-root re-exports as in the reference's src/lib.rs:16-23:
 plus rustyhgi_amd.entropy (device-side byte histogram of the grid) and rustyhgi_amd.Planes (device
 buffers placed for MI355X's HBM regions, include/hgi.h hgi_planes_alloc) and rustyhgi_amd.mapping (the 256-entry tables of
 Decoder.decode_mapped, include/hgi_map.h, and the constants of Encoder.encode_typed, include/hgi_typed.h).
+Encoder.requantize re-codes stored grids with another table in one launch (libhgi_requant.so, include/hgi_requant.h).
 All computation happens in libhgi_hip.so (hand-written HIP kernels); see include/hgi.h.
 """
 from . import entropy, interpolator, mapping, quantizator

@@ -478,6 +478,59 @@ class Encoder:
         _ffi_recon.check(st)
         return out, recon
 
+    def requantize(self, grids, out=None):
+        """Re-code GRIDS with this encoder's table: bit for bit `encode_view(Decoder(interpolator).decode_view(grids,
+        scale_level))`, without the decoded image ever reaching memory.  A grid stores dequantized residuals, so the quantizer
+        is a property of the encode alone; the grids must have been made with this encoder's interpolator and `scale_level`
+        (a change of either stays a decode and an encode by the caller).  `grids` and `out` are views as for `decode_view`
+        ((H, W) or (B, H, W) uint8, any row stride >= W); only the W-byte rows of `out` are written, the grids are not modified,
+        and `out` must not share memory with them.  CUDA tensors: ONE hgi_requant_dev launch (libhgi_requant.so), asynchronous on
+        the current stream -- 2 B/px instead of the 4 B/px of decode + encode.  What that launch does not serve
+        (HGI_EUNSUPPORTED: 0 or more than 8 levels, offsets beyond 32 bits, a width that is no multiple of 4 with the grids' last
+        bytes at the end of a 4-KiB page) is composed from `decode_view` into a temporary + `encode_view` on the same stream;
+        under the identity table the result is the source at ANY depth (decode is a bijection on grids and the identity encode
+        its inverse) and the rows are copied without a call of the library.  The same bytes, not fused.  numpy arrays are
+        uploaded and downloaded through torch tensors, synchronously.  Validated (ValueError) before any device call; empty
+        inputs need no device."""
+        what = "requantize"
+        lay = _view_layout(grids, what)
+        empty = lay[1] * lay[2] * lay[3] == 0
+        if out is None and not empty:
+            _view_device(grids, what)
+        out, olay = _view_out(out, grids, lay, what)
+        (src, b, h, w, sp, sfs, _), (dst, _, _, _, dp, dfs, _) = lay, olay
+        if empty:
+            return out
+        _view_device(grids, what)      # (a given `out` is judged first: its faults are the caller's to see on any machine)
+        if not _is_torch(grids):
+            import torch
+            if not torch.cuda.is_available():
+                raise _ffi.HgiError(_ffi.EDEVICE, "%s needs a GPU (there is no CPU fallback)" % what)
+            dev = self._ctx.device if self._ctx is not None else 0
+            t = torch.from_numpy(np.ascontiguousarray(grids)).to("cuda:%d" % dev)
+            out[...] = self.requantize(t).cpu().numpy()
+            return out
+        import torch
+        from . import _ffi_requant
+        dev = grids.device.index if grids.device.index is not None else torch.cuda.current_device()
+        if self._ctx is not None and self._ctx.device != dev:      # both routes judge the Encoder's context alike (_bind_ctx)
+            raise ValueError("tensor lives on cuda:%d but the context was created for cuda:%d" % (dev, self._ctx.device))
+        if 0 <= self.scale_level <= 31 and bool((self._lut == np.arange(256, dtype=np.uint8)).all()):
+            # The identity table keeps every residual d = a - p, and a and p are what the decoder made of the same grid: at any
+            # depth encode(decode(g), identity) == g (decode is a bijection on grids and this encode is its inverse).
+            out.copy_(grids)
+            return out
+        with torch.cuda.device(dev):
+            st = _ffi_requant.lib().hgi_requant_dev(
+                _ffi._vp(torch.cuda.current_stream(dev).cuda_stream or 0), src, sp, w, h, self.scale_level, self._interp,
+                self._lut.ctypes.data, dst, dp, b, sfs, dfs)
+        if st == _ffi.EUNSUPPORTED:      # not served by the one launch: the same bytes from two calls
+            image = Decoder(self.interpolator, context=self._ctx).decode_view(grids, self.scale_level)
+            self.encode_view(image, out=out)
+            return out
+        _ffi_requant.check(st)
+        return out
+
     def encode_typed(self, frames, scale=255.0, bias=0.0, out=None):
         """Encode float frames where they lie: a (H, W) or (B, H, W) torch CUDA tensor of float16, bfloat16 or float32 -- a view
         as for `encode_view`, strides counted in elements -- becomes the grids of the uint8 image `v = clamp(rint(x * scale +
