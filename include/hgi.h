@@ -229,9 +229,10 @@ HGI_API hgi_status hgi_decode_u8_pitched_dev(hgi_ctx *ctx, const void *d_grid, s
                                              size_t img_pitch, size_t batch, size_t grid_frame_stride,
                                              size_t img_frame_stride);
 /* One frame in host memory.  Synchronous.  Upload and download are 2-D copies of the width-byte rows     */
-/* only (the gaps are neither read nor written); between them the packed frame runs the uniform route --  */
-/* the host calls are transfer-bound.  Same argument rules as above with batch = 1; hgi_ctx_reserve for   */
-/* the frame's shape covers the scratch.                                                                  */
+/* only (the gaps are neither read nor written; the last row goes on its own, so that no copy names a     */
+/* byte behind the (height - 1) * pitch + width the array holds); between them the packed frame runs the  */
+/* uniform route -- the host calls are transfer-bound.  Same argument rules as above with batch = 1;      */
+/* hgi_ctx_reserve for the frame's shape covers the scratch.                                              */
 HGI_API hgi_status hgi_encode_u8_pitched(hgi_ctx *ctx, const uint8_t *img, size_t img_pitch, uint32_t width,
                                          uint32_t height, uint32_t levels, hgi_interp interp,
                                          const uint8_t lut[256], uint8_t *grid_out, size_t grid_pitch);

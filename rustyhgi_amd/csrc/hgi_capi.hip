@@ -239,7 +239,8 @@ hgi_status encode_impl(hgi_ctx *c, const uint8_t *img, uint32_t w, uint32_t h, u
     if (c->path == HGI_PATH_LEVELWISE) {
         uint8_t *rec = ws_take(c, batch * stride);
         if (!rec) return fail(HGI_ENOMEM, "scratch exhausted (level-wise reconstruction plane)");
-        HIP_TRY(launch_copy(img, rec, batch * stride, c->stream));
+        // (the caller's frames span (batch - 1) * stride + w * h bytes: nothing follows the last frame)
+        HIP_TRY(launch_copy(img, rec, (batch - 1) * stride + (size_t)w * h, c->stream));
         HIP_TRY(launch_seed(img, grid, f, levels, c->stream));
         for (uint32_t level = 0; level < levels; ++level)   // src/encoder.rs:45, sequential
             HIP_TRY(launch_encode_level(rec, grid, f, levels - level - 1, interp, l, c->stream));
@@ -1321,9 +1322,27 @@ hgi_status hgi_decode_u8_pitched_dev(hgi_ctx *c, const void *d_grid, size_t grid
     return pitched_decode_impl(c, static_cast<const uint8_t *>(d_grid), static_cast<uint8_t *>(d_img), f, levels, interp);
 }
 
+// Rows between the caller's pitched array and a packed device plane.  The caller's array ends with its last row ((height - 1) *
+// pitch + width bytes, include/hgi.h), so a 2-D copy of all `height` rows would describe a host rectangle of height * pitch bytes
+// that reaches pitch - width bytes past it -- pageable memory the runtime may pin and read as a whole (hgi_decode_scaled_u8 below;
+// DESIGN.md 4.14).  So the last row goes on its own; with pitch == width the rectangle is the array and one copy does.
+static hipError_t copy_host_rows(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t height, hipMemcpyKind kind,
+                                 hipStream_t s)
+{
+    const size_t host_pitch = kind == hipMemcpyHostToDevice ? spitch : dpitch;
+    if (host_pitch == width) return hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, kind, s);
+    if (height > 1) {
+        const hipError_t e = hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height - 1, kind, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipMemcpyAsync(static_cast<uint8_t *>(dst) + (height - 1) * dpitch, static_cast<const uint8_t *>(src) + (height - 1) * spitch, width,
+                          kind, s);
+}
+
 // One frame in host memory.  The host calls are transfer-bound: the width-byte rows go up with one 2-D copy into a
-// packed plane, the uniform route codes it, and the width-byte rows of the result come down with one 2-D copy -- the bytes
-// between the caller's rows are neither read nor written.  Sized by host_call_need, the formula hgi_ctx_reserve uses.
+// packed plane, the uniform route codes it, and the width-byte rows of the result come down with one 2-D copy (the last row on its
+// own each time: copy_host_rows) -- the bytes between the caller's rows are neither read nor written.  Sized by host_call_need,
+// the formula hgi_ctx_reserve uses.
 static hgi_status host_pitched(hgi_ctx *c, const uint8_t *in, size_t in_pitch, uint8_t *out, size_t out_pitch, uint32_t w, uint32_t h,
                                uint32_t levels, hgi_interp interp, const uint8_t *lut, bool encode)
 {
@@ -1339,12 +1358,12 @@ static hgi_status host_pitched(hgi_ctx *c, const uint8_t *in, size_t in_pitch, u
     c->ws_used = 0;
     uint8_t *d_in = ws_take(c, n), *d_out = ws_take(c, n);
     if (!d_in || !d_out) return fail(HGI_ENOMEM, "scratch exhausted (host staging)");
-    HIP_TRY(hipMemcpy2DAsync(d_in, w, in, in_pitch, w, h, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(copy_host_rows(d_in, w, in, in_pitch, w, h, hipMemcpyHostToDevice, c->stream));
     if (encode)
         HGI_TRY(encode_impl(c, d_in, w, h, levels, interp, lut, d_out, 1, n));
     else
         HGI_TRY(decode_impl(c, d_in, w, h, levels, interp, d_out, 1, n));
-    HIP_TRY(hipMemcpy2DAsync(out, out_pitch, d_out, w, w, h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(copy_host_rows(out, out_pitch, d_out, w, w, h, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return HGI_OK;
 }
