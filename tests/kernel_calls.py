@@ -1,5 +1,6 @@
 """The calls of every entry point that has a kernel of its own, as the GPU coverage suites make them (a helper module of
-tests/test_operand_coverage_gpu.py, tests/test_geometry_coverage_gpu.py and tests/test_tilewalk_gpu.py, not a conftest).
+tests/test_operand_coverage_gpu.py, tests/test_geometry_coverage_gpu.py, tests/test_tilewalk_gpu.py and
+tests/test_element_coverage_gpu.py, not a conftest).
 Outputs with a pitch are written into sentinel-filled parents that are checked whole; inputs with a pitch are read out of
 parents of random bytes.  Device tensors are compared on the device; the host report is made only on a mismatch."""
 import bisect
@@ -297,6 +298,45 @@ def run_typed(d_img_u8, d_grid, levels, interp, lut, E, kind, pair, what, w=None
     same_dev(dst.rows(), d_grid, name)
     dst.intact(name)
     assert torch.equal(src.buf, before), name + ": the image parent was modified"
+
+
+def run_typed_raw(d_bits, d_want, kind, pair, levels, interp, lut, what, gap=3, lead=3, extra=5, seed=0):
+    """hgi_typed_encode_dev on a batch of frames given as element bit patterns, taken as they are (run_typed lifts a uint8 design
+    through finite pre-images; this one serves frames that hold NaN, infinities and denormals on purpose).  `d_bits`: (B, h, w)
+    int16 / int32 on the device; `d_want`: the (B, h, w) expected grids.  The frames sit `lead` elements into a parent of random
+    bytes, rows `gap` elements and frames `extra` elements further apart than they need be; the grids go into a sentinel-filled
+    parent, rows and frames apart likewise, that is checked whole; the image parent must come back unchanged.  2-byte elements
+    of an odd width are kept off a page's end (the page rule of include/hgi_typed.h)."""
+    import torch
+    from rustyhgi_amd import _ffi_typed as T
+    E = ESIZE[kind]
+    B, h, w = d_bits.shape
+    assert d_bits.element_size() == E and tuple(d_want.shape) == (B, h, w)
+    pitch = (w + gap) * E
+    span = (h - 1) * pitch + w * E
+    fs = span + extra * E
+    gp = w + 61
+    gspan = (h - 1) * gp + w
+    gfs = gspan + 7
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(seed + 1)
+    buf = torch.randint(0, 256, (lead * E + (B - 1) * fs + span + 72,), dtype=torch.uint8, device="cuda", generator=gen)
+    off = lead * E
+    if E == 2 and w % 2 and (buf.data_ptr() + off + (B - 1) * fs + span) % PAGE == 0:
+        off += 4
+    assert (buf.data_ptr() + off) % E == 0
+    torch.as_strided(buf, (B, h, w * E), (fs, pitch, 1), off).copy_(d_bits.contiguous().view(torch.uint8).reshape(B, h, w * E))
+    before = buf.clone()
+    glead = 5
+    out = torch.full((glead + (B - 1) * gfs + gspan + 64,), SENT, dtype=torch.uint8, device="cuda")
+    T.check(T.lib().hgi_typed_encode_dev(torch.cuda.current_stream().cuda_stream or None, buf.data_ptr() + off, pitch, E, EKIND[kind], pair[0], pair[1],
+                                         w, h, levels, interp, lut.ctypes.data, out.data_ptr() + glead, gp, B, fs, gfs))
+    name = "%s typed %s x %r + %r L%d" % (what, kind, pair[0], pair[1], levels)
+    same_dev(torch.as_strided(out, (B, h, w), (gfs, gp, 1), glead), d_want, name)
+    c = out.clone()
+    torch.as_strided(c, (B, h, w), (gfs, gp, 1), glead).fill_(SENT)
+    assert bool((c == SENT).all()), name + ": bytes outside the grid rows written"
+    assert torch.equal(buf, before), name + ": the image parent was modified"
 
 
 def run_narrowed(ctx, oracle, img, d_img, levels, interp, lut, what, typed=None):
