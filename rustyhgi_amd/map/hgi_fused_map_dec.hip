@@ -18,6 +18,7 @@
 #include "../csrc/hgi_fused_dec.hip"   // the decode direction's build settings and tile procedure, 128 x 64 tiles
 #include "../csrc/hgi_fused_pitched.h"
 #pragma clang diagnostic pop
+#include "../companion/hgi_entry.h"
 #include "hgi_map_kernels.h"
 
 // Resident tiles per CU of a launch of 8 192 tiles and more (the dynamic LDS is padded to that: lds_for_waves).  The start is
@@ -247,15 +248,15 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(map_waves_pe
     const Tile tl = pitched_block_tile(p, edge, idle);
     if (idle) return;
     const u8 *fr = src + (size_t)tl.frame * p.sstride;
-    u8 *out = dst + (size_t)tl.frame * mp.ostride;
+    u8 *out = dst + (size_t)tl.frame * mp.x.stride;
     const PitchAt at = {p.sp};
     // 32-bit buffer offsets on both sides (the host launches nothing else)
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(fr), 0, p.srec, 0x00020000);
     const u32 rb = __builtin_amdgcn_readfirstlane(tl.Y0 * p.sp32 + tl.X0);
     MapOut mo;
-    mo.rd = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(out), 0, mp.orec, 0x00020000);
-    mo.P = mp.op32;
-    mo.base = __builtin_amdgcn_readfirstlane(tl.Y0 * mp.op32 + tl.X0 * (u32)E);
+    mo.rd = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(out), 0, mp.x.rec, 0x00020000);
+    mo.P = mp.x.pitch32;
+    mo.base = __builtin_amdgcn_readfirstlane(tl.Y0 * mp.x.pitch32 + tl.X0 * (u32)E);
     SeedRegs seeds;
     ConeLane cone;
     Stage st;
@@ -288,14 +289,6 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(map_waves_pe
         dec_tile_map<INTERP, E, 2>(buf, tab, tl, mo, st.o, k, W, H);
 }
 
-hipError_t map_static_lds_is_empty(const void *kernel)
-{
-    hipFuncAttributes fa;
-    const hipError_t e = hipFuncGetAttributes(&fa, kernel);
-    if (e != hipSuccess) return e;
-    return fa.sharedSizeBytes == 0 ? hipSuccess : hipErrorInvalidDeviceFunction;
-}
-
 }  // namespace
 
 hipError_t launch_decode_map(const uint8_t *grid, const void *table, void *out, const MapPlan &mp, uint32_t elem, uint32_t k,
@@ -326,7 +319,7 @@ hipError_t launch_decode_map(const uint8_t *grid, const void *table, void *out, 
     // the table's place is counted from LDS offset 0: checked once per instantiation on the host
 #define HGI_MAP(I, SE, EL)                                                                                            \
     do {                                                                                                              \
-        static const hipError_t lds0 = map_static_lds_is_empty(reinterpret_cast<const void *>(&k_dec_map<I, SE, EL>)); \
+        static const hipError_t lds0 = static_lds_is_empty(reinterpret_cast<const void *>(&k_dec_map<I, SE, EL>));    \
         if (lds0 != hipSuccess) return lds0;                                                                          \
         hipLaunchKernelGGL((k_dec_map<I, SE, EL>), blocks, b, lds, s, grid, tab, dst, k, sd, mp);                     \
     } while (0)

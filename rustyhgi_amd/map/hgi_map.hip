@@ -2,37 +2,13 @@
 // launch (hgi_fused_map_dec.hip).  Stateless: no ctx, no scratch, no environment.  Every argument rule is decided before the
 // first HIP call, the HGI_EINVAL rules before the HGI_EUNSUPPORTED ones.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <string.h>
 
 #include "../../include/hgi_map.h"
+#include "../companion/hgi_entry.h"
 #include "hgi_map_kernels.h"
 
 using namespace hgi;
-
-namespace {
-
-thread_local char g_err[512] = "";
-
-hgi_status fail(hgi_status st, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return st;
-}
-
-// How the pyramid is split between the tile and the cone: libhgi_hip.so's rule for one launch (csrc/hgi_capi.hip,
-// split_pyramid): up to five levels the tile holds the pyramid, six to eight are four fused levels under a cone.
-void split_levels(uint32_t levels, uint32_t *k, uint32_t *up)
-{
-    *k = levels < 6u ? levels : 4u;
-    *up = levels < 6u ? 0u : levels - 4u;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -63,13 +39,13 @@ hgi_status hgi_map_decode_dev(void *hip_stream, const void *d_grid, size_t grid_
     if (batch > 1 && (u128)out_frame_stride < ospan)
         return fail(HGI_EINVAL, "output frame stride %zu < (height - 1) * pitch + width * elem_size", out_frame_stride);
     // No aliasing, tested conservatively: the byte intervals of the grid, the output and the table must not meet.
-    const MapInterval gi = map_interval(reinterpret_cast<uintptr_t>(d_grid), width, height, grid_pitch, grid_frame_stride, batch);
-    const MapInterval oi = map_interval(reinterpret_cast<uintptr_t>(d_out), row, height, out_pitch, out_frame_stride, batch);
-    const MapInterval ti = map_table_interval(reinterpret_cast<uintptr_t>(d_table), elem_size);
+    const Interval gi = side_interval(reinterpret_cast<uintptr_t>(d_grid), width, height, grid_pitch, grid_frame_stride, batch);
+    const Interval oi = side_interval(reinterpret_cast<uintptr_t>(d_out), row, height, out_pitch, out_frame_stride, batch);
+    const Interval ti = table_interval(reinterpret_cast<uintptr_t>(d_table), 256u * (uint64_t)elem_size);
     if (gi.hi - gi.lo > (u128)SIZE_MAX || oi.hi - oi.lo > (u128)SIZE_MAX) return fail(HGI_EINVAL, "frame span too large");
-    if (map_meet(ti, oi)) return fail(HGI_EINVAL, "the table overlaps the output span: they must not alias");
-    if (map_meet(ti, gi)) return fail(HGI_EINVAL, "the table overlaps the grid span: they must not alias");
-    if (map_meet(gi, oi)) return fail(HGI_EINVAL, "the output span overlaps the grid span: they must not alias");
+    if (meet(ti, oi)) return fail(HGI_EINVAL, "the table overlaps the output span: they must not alias");
+    if (meet(ti, gi)) return fail(HGI_EINVAL, "the table overlaps the grid span: they must not alias");
+    if (meet(gi, oi)) return fail(HGI_EINVAL, "the output span overlaps the grid span: they must not alias");
     const MapFrames f = {width, height, (uint32_t)batch, elem_size, (uint64_t)grid_pitch, (uint64_t)out_pitch,
                          (uint64_t)grid_frame_stride, (uint64_t)out_frame_stride};
     const MapJudged j = map_plan(reinterpret_cast<uintptr_t>(d_grid), f);

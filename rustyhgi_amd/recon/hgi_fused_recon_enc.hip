@@ -15,6 +15,7 @@
 #include "../csrc/hgi_fused_enc.hip"   // the encode direction's build settings and tile procedure, 128 x 64 tiles
 #include "../csrc/hgi_fused_pitched.h"
 #pragma clang diagnostic pop
+#include "../companion/hgi_entry.h"
 #include "hgi_recon_kernels.h"
 
 namespace hgi {
@@ -181,7 +182,7 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(IDENT ? HGI_
     if (idle) return;
     const u8 *fr = src + (size_t)tl.frame * p.sstride;
     u8 *out = dst + (size_t)tl.frame * p.dstride;
-    u8 *rout = rec + (size_t)tl.frame * rp.rstride;
+    u8 *rout = rec + (size_t)tl.frame * rp.x.stride;
     const PitchAt at = {p.sp};
     u32 lutv = 0;
     SeedRegs seeds;
@@ -190,9 +191,9 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(IDENT ? HGI_
     u32 rb;
     TileCtx cur = {tl, pitched_buf(fr, out, p, tl, &rb)};
     ReconOut ro;
-    ro.rd = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(rout), 0, rp.rrec, 0x00020000);
-    ro.W = rp.rp32;
-    ro.base = __builtin_amdgcn_readfirstlane(tl.Y0 * rp.rp32 + tl.X0);
+    ro.rd = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(rout), 0, rp.x.rec, 0x00020000);
+    ro.W = rp.x.pitch32;
+    ro.base = __builtin_amdgcn_readfirstlane(tl.Y0 * rp.x.pitch32 + tl.X0);
     Stage st;
     if (!edge) {
         pitched_issue<false>(st, cur.b.rs, rb, p.sp32, W, tl, (int)k, nh);
@@ -221,14 +222,6 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(IDENT ? HGI_
         enc_tile_edge_recon<INTERP, IDENT, 2>(buf, rbuf, slut, cur, ro, st.o, k, W, H);
 }
 
-hipError_t recon_static_lds_is_empty(const void *kernel)
-{
-    hipFuncAttributes fa;
-    const hipError_t e = hipFuncGetAttributes(&fa, kernel);
-    if (e != hipSuccess) return e;
-    return fa.sharedSizeBytes == 0 ? hipSuccess : hipErrorInvalidDeviceFunction;
-}
-
 }  // namespace
 
 hipError_t launch_encode_recon(const uint8_t *img, uint8_t *grid, uint8_t *recon, const ReconPlan &rp, uint32_t k, uint32_t up,
@@ -244,7 +237,7 @@ hipError_t launch_encode_recon(const uint8_t *img, uint8_t *grid, uint8_t *recon
     // lut_at() addresses the table from LDS offset 0: checked once per instantiation on the host
 #define HGI_REC(I, ID, SE)                                                                                             \
     do {                                                                                                               \
-        static const hipError_t lds0 = recon_static_lds_is_empty(reinterpret_cast<const void *>(&k_enc_recon<I, ID, SE>)); \
+        static const hipError_t lds0 = static_lds_is_empty(reinterpret_cast<const void *>(&k_enc_recon<I, ID, SE>));   \
         if (lds0 != hipSuccess) return lds0;                                                                           \
         hipLaunchKernelGGL((k_enc_recon<I, ID, SE>), blocks, b, lds, s, img, grid, recon, k, lut, sd, rp);             \
     } while (0)

@@ -2,37 +2,13 @@
 // (hgi_recon_plan.h) and the one launch (hgi_fused_recon_enc.hip).  Stateless: no ctx, no scratch, no environment.
 // Every argument rule is decided before the first HIP call.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <string.h>
 
 #include "../../include/hgi_recon.h"
+#include "../companion/hgi_entry.h"
 #include "hgi_recon_kernels.h"
 
 using namespace hgi;
-
-namespace {
-
-thread_local char g_err[512] = "";
-
-hgi_status fail(hgi_status st, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return st;
-}
-
-// How the pyramid is split between the tile and the cone: libhgi_hip.so's rule for one launch (csrc/hgi_capi.hip,
-// split_pyramid): up to five levels the tile holds the pyramid, six to eight are four fused levels under a cone.
-void split_levels(uint32_t levels, uint32_t *k, uint32_t *up)
-{
-    *k = levels < 6u ? levels : 4u;
-    *up = levels < 6u ? 0u : levels - 4u;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -64,15 +40,15 @@ hgi_status hgi_recon_encode_u8_dev(void *hip_stream, const void *d_img, size_t i
     if (batch > 1 && (u128)recon_frame_stride < rspan)
         return fail(HGI_EINVAL, "reconstruction frame stride %zu < (height - 1) * pitch + width", recon_frame_stride);
     // No aliasing, tested conservatively: the byte intervals the three sides span must not meet.
-    const ReconInterval ii = recon_interval(reinterpret_cast<uintptr_t>(d_img), width, height, img_pitch, img_frame_stride, batch);
-    const ReconInterval gi = recon_interval(reinterpret_cast<uintptr_t>(d_grid), width, height, grid_pitch, grid_frame_stride, batch);
-    const ReconInterval ri = recon_interval(reinterpret_cast<uintptr_t>(d_recon), width, height, recon_pitch, recon_frame_stride, batch);
+    const Interval ii = side_interval(reinterpret_cast<uintptr_t>(d_img), width, height, img_pitch, img_frame_stride, batch);
+    const Interval gi = side_interval(reinterpret_cast<uintptr_t>(d_grid), width, height, grid_pitch, grid_frame_stride, batch);
+    const Interval ri = side_interval(reinterpret_cast<uintptr_t>(d_recon), width, height, recon_pitch, recon_frame_stride, batch);
     if (ii.hi - ii.lo > (u128)SIZE_MAX || gi.hi - gi.lo > (u128)SIZE_MAX || ri.hi - ri.lo > (u128)SIZE_MAX)
         return fail(HGI_EINVAL, "frame span too large");
     if (d_recon == d_img) return fail(HGI_EINVAL, "in-place (d_recon == d_img) is refused: a tile's halo reads its neighbours' original pixels (the spans overlap)");
-    if (recon_meet(ii, gi)) return fail(HGI_EINVAL, "the grid span overlaps the image span: they must not alias");
-    if (recon_meet(ii, ri)) return fail(HGI_EINVAL, "the reconstruction span overlaps the image span: they must not alias");
-    if (recon_meet(gi, ri)) return fail(HGI_EINVAL, "the reconstruction span overlaps the grid span: they must not alias");
+    if (meet(ii, gi)) return fail(HGI_EINVAL, "the grid span overlaps the image span: they must not alias");
+    if (meet(ii, ri)) return fail(HGI_EINVAL, "the reconstruction span overlaps the image span: they must not alias");
+    if (meet(gi, ri)) return fail(HGI_EINVAL, "the reconstruction span overlaps the grid span: they must not alias");
     const ReconFrames f = {width, height, (uint32_t)batch, (uint64_t)img_pitch, (uint64_t)grid_pitch, (uint64_t)recon_pitch,
                            (uint64_t)img_frame_stride, (uint64_t)grid_frame_stride, (uint64_t)recon_frame_stride};
     const ReconJudged j = recon_plan(reinterpret_cast<uintptr_t>(d_img), f);

@@ -23,6 +23,7 @@
 #include "../csrc/hgi_fused_enc.hip"   // the encode direction's build settings and tile procedure, 128 x 64 tiles
 #include "../csrc/hgi_fused_pitched.h"
 #pragma clang diagnostic pop
+#include "../companion/hgi_entry.h"
 #include "hgi_requant_kernels.h"
 
 namespace hgi {
@@ -245,14 +246,6 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(HGI_ENC_WAVE
     }
 }
 
-hipError_t requant_static_lds_is_empty(const void *kernel)
-{
-    hipFuncAttributes fa;
-    const hipError_t e = hipFuncGetAttributes(&fa, kernel);
-    if (e != hipSuccess) return e;
-    return fa.sharedSizeBytes == 0 ? hipSuccess : hipErrorInvalidDeviceFunction;
-}
-
 }  // namespace
 
 hipError_t launch_requant(const uint8_t *src, uint8_t *dst, const PitchedPlan &p, uint32_t k, uint32_t up, int interp,
@@ -268,7 +261,7 @@ hipError_t launch_requant(const uint8_t *src, uint8_t *dst, const PitchedPlan &p
     // lut_at() addresses the table from LDS offset 0: checked once per instantiation on the host
 #define HGI_RQ(I, SE)                                                                                                \
     do {                                                                                                             \
-        static const hipError_t lds0 = requant_static_lds_is_empty(reinterpret_cast<const void *>(&k_requant<I, SE>)); \
+        static const hipError_t lds0 = static_lds_is_empty(reinterpret_cast<const void *>(&k_requant<I, SE>));       \
         if (lds0 != hipSuccess) return lds0;                                                                         \
         hipLaunchKernelGGL((k_requant<I, SE>), blocks, b, lds, s, src, dst, k, lut, sd, p);                          \
     } while (0)

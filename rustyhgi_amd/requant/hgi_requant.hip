@@ -2,37 +2,13 @@
 // the one launch (hgi_fused_requant.hip).  Stateless: no ctx, no scratch, no environment.  Every argument rule is decided before
 // the first HIP call, the HGI_EINVAL rules before the HGI_EUNSUPPORTED ones.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <string.h>
 
 #include "../../include/hgi_requant.h"
+#include "../companion/hgi_entry.h"
 #include "hgi_requant_kernels.h"
 
 using namespace hgi;
-
-namespace {
-
-thread_local char g_err[512] = "";
-
-hgi_status fail(hgi_status st, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return st;
-}
-
-// How the pyramid is split between the tile and the cone: libhgi_hip.so's rule for one launch (csrc/hgi_capi.hip,
-// split_pyramid): up to five levels the tile holds the pyramid, six to eight are four fused levels under a cone.
-void split_levels(uint32_t levels, uint32_t *k, uint32_t *up)
-{
-    *k = levels < 6u ? levels : 4u;
-    *up = levels < 6u ? 0u : levels - 4u;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -56,10 +32,10 @@ hgi_status hgi_requant_dev(void *hip_stream, const void *d_src, size_t src_pitch
     if (batch > 1 && (u128)dst_frame_stride < dspan)
         return fail(HGI_EINVAL, "destination frame stride %zu < (height - 1) * pitch + width", dst_frame_stride);
     // No aliasing, tested conservatively: the byte intervals the two sides span must not meet.
-    const RequantInterval si = requant_interval(reinterpret_cast<uintptr_t>(d_src), width, height, src_pitch, src_frame_stride, batch);
-    const RequantInterval di = requant_interval(reinterpret_cast<uintptr_t>(d_dst), width, height, dst_pitch, dst_frame_stride, batch);
+    const Interval si = side_interval(reinterpret_cast<uintptr_t>(d_src), width, height, src_pitch, src_frame_stride, batch);
+    const Interval di = side_interval(reinterpret_cast<uintptr_t>(d_dst), width, height, dst_pitch, dst_frame_stride, batch);
     if (si.hi - si.lo > (u128)SIZE_MAX || di.hi - di.lo > (u128)SIZE_MAX) return fail(HGI_EINVAL, "frame span too large");
-    if (requant_meet(si, di))
+    if (meet(si, di))
         return fail(HGI_EINVAL, d_dst == d_src ? "in-place (d_dst == d_src) is refused: a tile's halo reads its neighbours' source residuals (the spans overlap)"
                                                : "the destination span overlaps the source span: they must not alias");
     const RequantFrames f = {width, height, (uint32_t)batch, (uint64_t)src_pitch, (uint64_t)dst_pitch, (uint64_t)src_frame_stride,

@@ -30,6 +30,7 @@
 #include "../csrc/hgi_fused_enc.hip"   // the encode direction's build settings and tile procedure, 128 x 64 tiles
 #include "../csrc/hgi_fused_pitched.h"
 #pragma clang diagnostic pop
+#include "../companion/hgi_entry.h"
 #include "hgi_typed_kernels.h"
 
 namespace hgi {
@@ -352,26 +353,26 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(kTypedWavesP
     bool edge, idle;
     const Tile tl = pitched_block_tile(p, edge, idle);
     if (idle) return;
-    const u8 *fr = src + (size_t)tl.frame * tp.istride;
+    const u8 *fr = src + (size_t)tl.frame * tp.x.stride;
     u8 *out = dst + (size_t)tl.frame * p.dstride;
     SeedRegs seeds;
     ConeLane cone;
     // 32-bit buffer offsets on both sides (the host launches nothing else): bytes on the image side, pixels on the grid's
     TileCtx cur;
     cur.tl = tl;
-    cur.b.rs = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(fr), 0, tp.irec, 0x00020000);
+    cur.b.rs = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(fr), 0, tp.x.rec, 0x00020000);
     cur.b.rd = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(out), 0, p.drec, 0x00020000);
     cur.b.W = p.dp32;
     cur.b.base = __builtin_amdgcn_readfirstlane(tl.Y0 * p.dp32 + tl.X0);
-    const u32 rb = __builtin_amdgcn_readfirstlane(tl.Y0 * tp.ip32 + tl.X0 * E);
+    const u32 rb = __builtin_amdgcn_readfirstlane(tl.Y0 * tp.x.pitch32 + tl.X0 * E);
     Stage st;
     u32 lutv = 0;
     if (!edge) {
         constexpr int NB = typed_batch(E);
         RawOdd<E> ro;
-        typed_issue<E, false>(st, cur.b.rs, rb, tp.ip32, W, H, tl, (int)k, nh, cv);
-        typed_issue_odd<E>(ro, cur.b.rs, rb, tp.ip32, 0);
-        if (SEEDED == 2) cone = cone_issue_typed<E>(cur.b.rs, tp.ip32, W, H, sd, tl);
+        typed_issue<E, false>(st, cur.b.rs, rb, tp.x.pitch32, W, H, tl, (int)k, nh, cv);
+        typed_issue_odd<E>(ro, cur.b.rs, rb, tp.x.pitch32, 0);
+        if (SEEDED == 2) cone = cone_issue_typed<E>(cur.b.rs, tp.x.pitch32, W, H, sd, tl);
         if (!IDENT) lutv = lut.w[HGI_LANE];
         stage_commit<true>(buf, rbuf, st, nh);
         if (!IDENT) reinterpret_cast<u32 *>(slut)[HGI_LANE] = lutv;
@@ -379,7 +380,7 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(kTypedWavesP
         typed_convert_odd<E>(st, ro, cv, 0);
         if (NB < NFINE) {
             __builtin_amdgcn_sched_barrier(0);
-            typed_issue_odd<E>(ro, cur.b.rs, rb, tp.ip32, NB);
+            typed_issue_odd<E>(ro, cur.b.rs, rb, tp.x.pitch32, NB);
         }
         if (SEEDED == 2) {
             cone_convert_typed<E>(cone, cv);
@@ -390,8 +391,8 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(kTypedWavesP
         enc_tile_fast<INTERP, IDENT>(buf, rbuf, slut, cur, st.o, k, W, H);
         return;
     }
-    if (SEEDED == 2) cone = cone_issue_typed<E>(cur.b.rs, tp.ip32, W, H, sd, tl);
-    typed_issue<E, true>(st, cur.b.rs, rb, tp.ip32, W, H, tl, (int)k, nh, cv);
+    if (SEEDED == 2) cone = cone_issue_typed<E>(cur.b.rs, tp.x.pitch32, W, H, sd, tl);
+    typed_issue<E, true>(st, cur.b.rs, rb, tp.x.pitch32, W, H, tl, (int)k, nh, cv);
     if (!IDENT) lutv = lut.w[HGI_LANE];
     stage_commit<true>(buf, rbuf, st, nh);
     if (!IDENT) reinterpret_cast<u32 *>(slut)[HGI_LANE] = lutv;
@@ -405,14 +406,6 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(kTypedWavesP
         enc_tile_edge<INTERP, IDENT, 1>(buf, rbuf, slut, cur, st.o, k, W, H);
     else
         enc_tile_edge<INTERP, IDENT, 2>(buf, rbuf, slut, cur, st.o, k, W, H);
-}
-
-hipError_t typed_static_lds_is_empty(const void *kernel)
-{
-    hipFuncAttributes fa;
-    const hipError_t e = hipFuncGetAttributes(&fa, kernel);
-    if (e != hipSuccess) return e;
-    return fa.sharedSizeBytes == 0 ? hipSuccess : hipErrorInvalidDeviceFunction;
 }
 
 }  // namespace
@@ -432,7 +425,7 @@ hipError_t launch_encode_typed(const void *img, uint8_t *grid, const TypedPlan &
     // lut_at() addresses the table from LDS offset 0: checked once per instantiation on the host
 #define HGI_TYP(I, ID, SE, EL)                                                                                               \
     do {                                                                                                                     \
-        static const hipError_t lds0 = typed_static_lds_is_empty(reinterpret_cast<const void *>(&k_enc_typed<I, ID, SE, EL>)); \
+        static const hipError_t lds0 = static_lds_is_empty(reinterpret_cast<const void *>(&k_enc_typed<I, ID, SE, EL>));     \
         if (lds0 != hipSuccess) return lds0;                                                                                 \
         hipLaunchKernelGGL((k_enc_typed<I, ID, SE, EL>), blocks, b, lds, s, src, grid, k, lut, sd, tp, cv);                  \
     } while (0)

@@ -3,37 +3,13 @@
 // the first HIP call, the HGI_EINVAL rules before the HGI_EUNSUPPORTED ones.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <string.h>
 
 #include "../../include/hgi_typed.h"
+#include "../companion/hgi_entry.h"
 #include "hgi_typed_kernels.h"
 
 using namespace hgi;
-
-namespace {
-
-thread_local char g_err[512] = "";
-
-hgi_status fail(hgi_status st, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return st;
-}
-
-// How the pyramid is split between the tile and the cone: libhgi_hip.so's rule for one launch (csrc/hgi_capi.hip,
-// split_pyramid): up to five levels the tile holds the pyramid, six to eight are four fused levels under a cone.
-void split_levels(uint32_t levels, uint32_t *k, uint32_t *up)
-{
-    *k = levels < 6u ? levels : 4u;
-    *up = levels < 6u ? 0u : levels - 4u;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -67,10 +43,10 @@ hgi_status hgi_typed_encode_dev(void *hip_stream, const void *d_img, size_t img_
     if (batch > 1 && (u128)grid_frame_stride < gspan)
         return fail(HGI_EINVAL, "grid frame stride %zu < (height - 1) * pitch + width", grid_frame_stride);
     // No aliasing, tested conservatively: the byte intervals of the image and the grid must not meet.
-    const TypedInterval ii = typed_interval(reinterpret_cast<uintptr_t>(d_img), row, height, img_pitch, img_frame_stride, batch);
-    const TypedInterval gi = typed_interval(reinterpret_cast<uintptr_t>(d_grid), width, height, grid_pitch, grid_frame_stride, batch);
+    const Interval ii = side_interval(reinterpret_cast<uintptr_t>(d_img), row, height, img_pitch, img_frame_stride, batch);
+    const Interval gi = side_interval(reinterpret_cast<uintptr_t>(d_grid), width, height, grid_pitch, grid_frame_stride, batch);
     if (ii.hi - ii.lo > (u128)SIZE_MAX || gi.hi - gi.lo > (u128)SIZE_MAX) return fail(HGI_EINVAL, "frame span too large");
-    if (typed_meet(ii, gi)) return fail(HGI_EINVAL, "the grid span overlaps the image span: they must not alias");
+    if (meet(ii, gi)) return fail(HGI_EINVAL, "the grid span overlaps the image span: they must not alias");
     const TypedFrames f = {width, height, (uint32_t)batch, elem_size, (uint64_t)img_pitch, (uint64_t)grid_pitch,
                            (uint64_t)img_frame_stride, (uint64_t)grid_frame_stride};
     const TypedJudged j = typed_plan(reinterpret_cast<uintptr_t>(d_img), f);

@@ -1,6 +1,6 @@
 // Typed encode (hgi_typed_encode_dev, include/hgi_typed.h): the host plan of the launch -- the image of E-byte elements read
-// through a BYTE pitch of its own, the grid written through its pitch -- and the byte-interval test of the call.  On top of the
-// pitched plan (csrc/hgi_pitched.h): pitched_plan judges the grid side in pixels and owns the tile list, the block -> tile map
+// through a BYTE pitch of its own, the grid written through its pitch.  The bound of a side, the page rule and the byte-interval
+// test of the call are companion/hgi_sides.h's.  On top of the pitched plan (csrc/hgi_pitched.h): pitched_plan judges the grid side in pixels and owns the tile list, the block -> tile map
 // and the launch order as they stand; this adds the image side in bytes.  Plain C++: tests/cpp/test_typed_plan.cpp runs it
 // with g++.
 //
@@ -10,7 +10,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "../csrc/hgi_pitched.h"
+#include "../companion/hgi_sides.h"
 
 namespace hgi {
 
@@ -24,9 +24,9 @@ struct TypedFrames {
 // is not used) and the image's side.
 struct TypedPlan {
     PitchedPlan p;
-    uint32_t ip32, irec;          // read pitch and num_records (span + tail) of the image's descriptor, bytes
-    uint64_t istride;
+    ExtraSide x;                  // the image: read pitch, num_records (span + tail) of its descriptor, frame stride, bytes
 };
+static_assert(extra_side_layout<TypedPlan>(), "a kernel argument: its layout is the kernels'");
 
 // What the host decides on: the plan, and why its `p.fast` is what it is.
 struct TypedJudged {
@@ -35,29 +35,11 @@ struct TypedJudged {
     bool fits32, tail_ok;
 };
 
-// Every 32-bit buffer offset the tile procedure forms on a side whose rows lie `pitch` bytes apart (pitched_plan's bound,
-// recon_fits32; on the image side the largest is (Y0 + 64 + 64) * pitch + (X0 + 128 + 64 + 16) * E <= (height + 129) * pitch + 832).
-inline bool typed_fits32(uint32_t height, uint64_t pitch)
-{
-    return pitch < (1ull << 32) && ((uint64_t)height + 2 * kPitchedTileH + 64) * pitch + 1024 < (1ull << 32);
-}
-
-// Bytes from an image frame's first byte to its last.
-inline uint64_t typed_img_span(uint32_t w, uint32_t h, uint32_t elem, uint64_t pitch) { return (uint64_t)(h - 1) * pitch + (uint64_t)w * elem; }
-
 // E = 2 and an odd width: the dword that holds a row's last element straddles the row's end -- on the last row, the span's end
 // -- and the range check would drop it whole, so the descriptor gets 2 extra records.  Behind every frame but the last they lie
 // in the next frame or the stride padding; behind the last frame they must stay in the 4-KiB page of its last byte, i.e. the
 // span must not end on a page boundary.  E = 4: dwords of 4-byte-aligned elements never straddle the span's end.
 inline bool typed_tail_needed(const TypedFrames &f) { return f.elem == 2 && (f.width & 1u); }
-
-inline bool typed_tail_ok(uint64_t img, const TypedFrames &f)
-{
-    const uint64_t ip = f.height > 1 ? f.img_pitch : (uint64_t)f.width * f.elem, stride = f.batch > 1 ? f.img_stride : 0;
-    const uint64_t span = typed_img_span(f.width, f.height, f.elem, ip);
-    const uint64_t end = img + (uint64_t)(f.batch - 1) * stride + span;
-    return ((end - 1) >> 12) == ((end + 1) >> 12) && (f.batch == 1 || stride >= span);
-}
 
 // The pitched plan of a side that is only WRITTEN.  pitched_plan takes the address of the side it READS, for one purpose: its
 // rule about the three bytes read behind the last frame's span (widths that are no multiple of 4).  The grid of a typed encode
@@ -78,34 +60,15 @@ inline TypedJudged typed_plan(uint64_t img, const TypedFrames &f)
     TypedJudged r = {};
     const PitchedFrames pf = {f.width, f.height, f.batch, f.grid_pitch, f.grid_pitch, f.grid_stride, f.grid_stride};
     r.ip = f.height > 1 ? f.img_pitch : (uint64_t)f.width * f.elem;
-    r.ispan = typed_img_span(f.width, f.height, f.elem, r.ip);
+    r.ispan = side_span((uint64_t)f.width * f.elem, f.height, r.ip);
     const uint64_t gp = f.height > 1 ? f.grid_pitch : f.width;
-    r.fits32 = typed_fits32(f.height, gp) && typed_fits32(f.height, r.ip);
-    r.tail_ok = !typed_tail_needed(f) || typed_tail_ok(img, f);
+    r.fits32 = side_fits32(f.height, gp) && side_fits32(f.height, r.ip);
+    r.tail_ok = !typed_tail_needed(f) || tail_in_page(img, (uint64_t)f.width * f.elem, f.height, f.img_pitch, f.img_stride, f.batch, 2);
     // `fast` holds only if both sides fit and the image's tail rule holds: the pitched plan is made as the checked plan (no
     // 32-bit pitches, no records, no interior tiles) otherwise, so that it never describes a buffer path that does not exist.
     r.plan.p = typed_grid_plan(pf, !(r.fits32 && r.tail_ok));
-    r.plan.istride = f.batch > 1 ? f.img_stride : 0;
-    r.plan.ip32 = r.plan.p.fast ? (uint32_t)r.ip : 0u;
-    r.plan.irec = r.plan.p.fast ? (uint32_t)r.ispan + (typed_tail_needed(f) ? 2u : 0u) : 0u;
+    r.plan.x = extra_side(r.plan.p.fast, r.ip, r.ispan + (typed_tail_needed(f) ? 2u : 0u), f.batch > 1 ? f.img_stride : 0);
     return r;
 }
-
-// ---- byte intervals of a call: first byte of the first frame to last byte of the last; `row` bytes per row ----------------
-struct TypedInterval {
-    unsigned __int128 lo, hi;     // [lo, hi)
-};
-
-inline TypedInterval typed_interval(uint64_t ptr, uint64_t row, uint32_t h, uint64_t pitch, uint64_t stride, uint64_t batch)
-{
-    typedef unsigned __int128 u128;
-    const u128 span = (u128)(h - 1) * pitch + row;
-    TypedInterval i;
-    i.lo = ptr;
-    i.hi = (u128)ptr + (u128)(batch - 1) * (batch > 1 ? stride : 0) + span;
-    return i;
-}
-
-inline bool typed_meet(const TypedInterval &a, const TypedInterval &b) { return a.lo < b.hi && b.lo < a.hi; }
 
 }  // namespace hgi

@@ -1,7 +1,6 @@
-// rustyhgi_amd/map/hgi_map_plan.h -- the two-sided plan of mapped decode and its interval tests -- on random shapes, pitches,
+// rustyhgi_amd/map/hgi_map_plan.h -- the two-sided plan of mapped decode -- on random shapes, pitches,
 // alignments, batches and element sizes:
-//   * every block of a launch walked through pitched_tile(): every tile of every frame covered exactly once, interior tiles with
-//     their body inside the image, idle blocks only in the padding behind the ragged tiles;
+//   * every block of a launch walked through pitched_tile() (walk_launch, plan_test_util.h);
 //   * `fast` against the documented rule evaluated here from scratch (include/hgi_map.h): the grid pitch and the output pitch in
 //     BYTES within the 32-bit bound, and -- width % 4 != 0 -- the three bytes behind the last grid frame's span in the page of
 //     its last byte; fits32 / tail_ok say which half failed;
@@ -9,45 +8,14 @@
 //     output side's (Y0 + 63) * pitch + (X0 + 128) * E for every block -- fits 32 bits when computed in 64; the write
 //     descriptor holds exactly the output span, the read descriptor the grid span plus 0 or 3 bytes; every byte of every row a
 //     tile stores inside the image lies below the records, and a row at or below the image's height starts at or beyond them;
-//   * the interval tests against brute force: small layouts painted byte by byte into a map -- two of the grid, the output and
-//     the table meet iff a byte of one lies between the first and the last byte of the other.
+// The byte intervals of the call, the page rule and the bound themselves are companion/hgi_sides.h's: test_sides.cpp.
 // Usage: test_map_plan [cases] [seed]
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
 #include "../../rustyhgi_amd/map/hgi_map_plan.h"
+#include "plan_test_util.h"
 
 using namespace hgi;
 
 namespace {
-
-uint64_t g_x = 0x9E3779B97F4A7C15ull;
-uint64_t rnd()
-{
-    g_x ^= g_x << 13;
-    g_x ^= g_x >> 7;
-    g_x ^= g_x << 17;
-    return g_x;
-}
-uint64_t rnd_in(uint64_t lo, uint64_t hi) { return lo + rnd() % (hi - lo + 1); }
-
-int g_bad = 0;
-#define CHECK(cond, ...)                                   \
-    do {                                                   \
-        if (!(cond)) {                                     \
-            if (g_bad < 20) {                              \
-                std::printf("FAIL %s: ", #cond);           \
-                std::printf(__VA_ARGS__);                  \
-                std::printf("\n");                         \
-            }                                              \
-            ++g_bad;                                       \
-        }                                                  \
-    } while (0)
-
-// the header's rule for one side, restated
-bool side_fits(uint32_t h, uint64_t pitch) { return pitch < (1ull << 32) && ((uint64_t)h + 192) * pitch + 1024 < (1ull << 32); }
 
 void plan_case(int i)
 {
@@ -85,8 +53,7 @@ void plan_case(int i)
     if (!p.ok) return;
     CHECK(p.tx == (f.width + 127) / 128 && p.ty == (f.height + 63) / 64, "case %d: tiles %u x %u", i, p.tx, p.ty);
     CHECK(p.sp == gp && j.op == op && j.ospan == ospan, "case %d: pitches", i);
-    CHECK(map_out_span(f.width, f.height, E, op) == ospan, "case %d: output span", i);
-    CHECK(p.sstride == (f.batch > 1 ? f.grid_stride : 0) && r.ostride == (f.batch > 1 ? f.out_stride : 0), "case %d: strides", i);
+    CHECK(p.sstride == (f.batch > 1 ? f.grid_stride : 0) && r.x.stride == (f.batch > 1 ? f.out_stride : 0), "case %d: strides", i);
     // the documented rule, from scratch
     const uint64_t end = src + (uint64_t)(f.batch - 1) * (f.batch > 1 ? f.grid_stride : 0) + gspan;
     const bool fits = side_fits(f.height, gp) && side_fits(f.height, op);
@@ -100,105 +67,37 @@ void plan_case(int i)
               (unsigned long long)ymax, (unsigned long long)gp);
         CHECK(ymax * op + xmax * E < (1ull << 32), "case %d: output side: 32-bit offset overflow (%llu rows, pitch %llu)", i,
               (unsigned long long)ymax, (unsigned long long)op);
-        CHECK(p.sp32 == gp && r.op32 == op, "case %d: 32-bit pitches", i);
-        CHECK(r.orec == ospan, "case %d: write records %u, span %llu", i, r.orec, (unsigned long long)ospan);
+        CHECK(p.sp32 == gp && r.x.pitch32 == op, "case %d: 32-bit pitches", i);
+        CHECK(r.x.rec == ospan, "case %d: write records %u, span %llu", i, r.x.rec, (unsigned long long)ospan);
         CHECK(p.srec == gspan + (f.width % 4 ? 3 : 0), "case %d: read records %u, span %llu", i, p.srec, (unsigned long long)gspan);
         CHECK((uint64_t)f.height * gp >= gspan && (uint64_t)f.height * op >= ospan, "case %d: row H inside a span", i);
-        CHECK(op % E == 0 && r.ostride % E == 0, "case %d: whole elements", i);
+        CHECK(op % E == 0 && r.x.stride % E == 0, "case %d: whole elements", i);
     } else {
         // a refused plan describes no buffer path on either side
-        CHECK(r.op32 == 0 && r.orec == 0 && p.sp32 == 0 && p.srec == 0 && p.ix == 0 && p.iy == 0 && p.nf == 0,
+        CHECK(r.x.pitch32 == 0 && r.x.rec == 0 && p.sp32 == 0 && p.srec == 0 && p.ix == 0 && p.iy == 0 && p.nf == 0,
               "case %d: descriptors of a refused plan", i);
         return;     // nothing is launched
     }
     CHECK(p.nf == p.ipf * f.batch && p.nedge == (tpf - p.ipf) * f.batch && p.ipf == p.ix * p.iy, "case %d: totals", i);
     CHECK(p.ix == (f.width / 128) * (p.iy ? 1 : 0) && p.iy == (f.height / 64) * (p.ix ? 1 : 0), "case %d: interior %u x %u", i, p.ix, p.iy);
-    // walk the launch
-    const uint64_t blocks = pitched_blocks(p);
-    std::vector<uint8_t> seen((size_t)(tpf * f.batch), 0);
-    uint64_t idle = 0;
-    for (uint64_t b = 0; b < blocks; ++b) {
-        const PitchedTile t = pitched_tile(p, (uint32_t)b);
-        if (t.idle) {
-            CHECK(b >= p.nedge && b < ((p.nedge + 7u) & ~7u), "case %d: idle block %llu outside the padding", i, (unsigned long long)b);
-            ++idle;
-            continue;
-        }
-        CHECK(t.frame < f.batch && t.X0 % 128 == 0 && t.Y0 % 64 == 0 && t.X0 < f.width && t.Y0 < f.height,
-              "case %d: block %llu -> frame %u tile (%u, %u)", i, (unsigned long long)b, t.frame, t.X0, t.Y0);
-        if (!(t.frame < f.batch && t.X0 < f.width && t.Y0 < f.height)) continue;
-        const bool inside = (uint64_t)t.X0 + 128 <= f.width && (uint64_t)t.Y0 + 64 <= f.height;
-        CHECK(t.edge != inside, "case %d: block %llu: edge %d, body inside %d", i, (unsigned long long)b, (int)t.edge, (int)inside);
-        // the tile's origin on both sides, as the kernel forms it (32-bit arithmetic)
-        const uint32_t gbase = t.Y0 * p.sp32 + t.X0, obase = t.Y0 * r.op32 + t.X0 * E;
-        CHECK(gbase == (uint64_t)t.Y0 * gp + t.X0, "case %d: grid side: tile origin wraps", i);
-        CHECK(obase == (uint64_t)t.Y0 * op + (uint64_t)t.X0 * E, "case %d: output side: tile origin wraps", i);
+    // walk the launch: the tile's origin on both sides (pixels on the grid side, bytes on the output's)
+    const WalkSide sides[2] = {{"grid", p.sp32, gp, 1}, {"output", r.x.pitch32, op, E}};
+    walk_launch(i, p, f.width, f.height, f.batch, sides, 2, [&](const PitchedTile &t, uint64_t b) {
+        const uint32_t obase = t.Y0 * r.x.pitch32 + t.X0 * E;
         // the last row the tile stores inside the image, its last element: the offset fits 32 bits and lies below the records;
         // the row below the image (if the tile reaches it) starts at or beyond them
         const uint32_t ylast = (t.Y0 + 63 < f.height ? t.Y0 + 63 : f.height - 1) - t.Y0;
         const uint32_t xend = (t.X0 + 128 < f.width ? t.X0 + 128 : f.width) - t.X0;
         const uint64_t last64 = (uint64_t)obase + (uint64_t)ylast * op + (uint64_t)xend * E;
-        const uint32_t last32 = obase + ylast * r.op32 + xend * E;
-        CHECK(last64 == last32 && last64 <= r.orec, "case %d: block %llu: last stored byte %llu, records %u", i, (unsigned long long)b,
-              (unsigned long long)last64, r.orec);
+        const uint32_t last32 = obase + ylast * r.x.pitch32 + xend * E;
+        CHECK(last64 == last32 && last64 <= r.x.rec, "case %d: block %llu: last stored byte %llu, records %u", i, (unsigned long long)b,
+              (unsigned long long)last64, r.x.rec);
         if (t.Y0 + 64 > f.height) {
             const uint64_t below = (uint64_t)f.height * op + (uint64_t)t.X0 * E;
-            CHECK(below >= r.orec && below + 63 * op + 128 * E < (1ull << 32), "case %d: block %llu: a row below the image inside the records", i,
+            CHECK(below >= r.x.rec && below + 63 * op + 128 * E < (1ull << 32), "case %d: block %llu: a row below the image inside the records", i,
                   (unsigned long long)b);
         }
-        uint8_t &s = seen[(size_t)(t.frame * tpf + (uint64_t)(t.Y0 / 64) * p.tx + t.X0 / 128)];
-        CHECK(s == 0, "case %d: tile covered twice", i);
-        s = 1;
-    }
-    CHECK(idle == ((p.nedge + 7u) & ~7u) - p.nedge, "case %d: %llu idle blocks", i, (unsigned long long)idle);
-    for (size_t k = 0; k < seen.size(); ++k) CHECK(seen[k] == 1, "case %d: tile %zu not covered", i, k);
-}
-
-// The grid, the output and the table somewhere in a 64-KiB arena; brute force: paint each one's conservative interval (first
-// byte to last byte) and compare with map_meet.
-void interval_case(int i)
-{
-    const uint32_t N = 1u << 16;
-    const uint32_t w = (uint32_t)rnd_in(1, 40), h = (uint32_t)rnd_in(1, 12), batch = (uint32_t)rnd_in(1, 3), E = rnd() % 2 ? 2u : 4u;
-    MapInterval iv[3];
-    std::vector<uint8_t> paint[3];
-    uint64_t prev_ptr = 0, prev_total = 1;
-    for (int k = 0; k < 3; ++k) {
-        const uint64_t row = k == 1 ? (uint64_t)w * E : w;
-        const uint64_t pitch = row + (k == 1 ? E : 1) * rnd_in(0, 30);
-        const uint64_t span = (uint64_t)(h - 1) * pitch + row;
-        const uint64_t stride = span + (k == 1 ? E : 1) * rnd_in(0, 50);
-        const uint64_t total = k == 2 ? 256ull * E : (uint64_t)(batch - 1) * stride + span;
-        // near or on one another every other case
-        uint64_t ptr = k && rnd() % 2 ? prev_ptr + rnd_in(0, 2 * prev_total) : rnd_in(0, N - total - 1);
-        if (ptr + total > N) ptr = N - total;
-        iv[k] = k == 2 ? map_table_interval(ptr, E) : map_interval(ptr, row, h, pitch, stride, batch);
-        paint[k].assign(N, 0);
-        uint64_t first = N, last = 0;
-        if (k == 2) {
-            first = ptr;
-            last = ptr + 256ull * E - 1;
-        } else {
-            for (uint32_t b = 0; b < batch; ++b)
-                for (uint32_t y = 0; y < h; ++y)
-                    for (uint64_t x = 0; x < row; ++x) {
-                        const uint64_t a = ptr + b * stride + y * pitch + x;
-                        first = a < first ? a : first;
-                        last = a > last ? a : last;
-                    }
-        }
-        for (uint64_t a = first; a <= last; ++a) paint[k][a] = 1;
-        CHECK(iv[k].lo == first && iv[k].hi == last + 1, "interval %d side %d: [%llu, %llu) painted [%llu, %llu]", i, k,
-              (unsigned long long)iv[k].lo, (unsigned long long)iv[k].hi, (unsigned long long)first, (unsigned long long)last);
-        prev_ptr = ptr;
-        prev_total = total;
-    }
-    for (int a = 0; a < 3; ++a)
-        for (int b = a + 1; b < 3; ++b) {
-            bool meet = false;
-            for (uint32_t j = 0; j < N && !meet; ++j) meet = paint[a][j] && paint[b][j];
-            CHECK(map_meet(iv[a], iv[b]) == meet && map_meet(iv[b], iv[a]) == meet, "interval %d: sides %d / %d: meet %d", i, a, b, (int)meet);
-        }
+    });
 }
 
 }  // namespace
@@ -208,16 +107,15 @@ int main(int argc, char **argv)
     const int cases = argc > 1 ? std::atoi(argv[1]) : 300;
     if (argc > 2) g_x ^= std::strtoull(argv[2], nullptr, 0);
     for (int i = 0; i < cases; ++i) plan_case(i);
-    for (int i = 0; i < cases; ++i) interval_case(i);
     {
         // the output side alone pushes the offsets past 32 bits: refused, never narrowed (4096 elements of 4 bytes, 2^18 apart)
         MapFrames f = {4096u, 4096u, 2u, 4u, 4096, 1ull << 20, 1ull << 24, 1ull << 32};
         const MapJudged r = map_plan(0x7f0000000000ull, f);
-        CHECK(r.plan.p.ok && !r.plan.p.fast && !r.fits32 && r.tail_ok && r.plan.op32 == 0 && r.plan.orec == 0 && r.plan.p.sp32 == 0 &&
+        CHECK(r.plan.p.ok && !r.plan.p.fast && !r.fits32 && r.tail_ok && r.plan.x.pitch32 == 0 && r.plan.x.rec == 0 && r.plan.p.sp32 == 0 &&
                   r.plan.p.nf == 0, "a 2^20-byte output pitch on 4096 rows must be refused, on both sides");
         f.out_pitch = 1ull << 19;
         const MapJudged q = map_plan(0x7f0000000000ull, f);
-        CHECK(q.plan.p.fast && q.fits32 && q.plan.op32 == (1u << 19), "a 2^19-byte output pitch on 4096 rows fits");
+        CHECK(q.plan.p.fast && q.fits32 && q.plan.x.pitch32 == (1u << 19), "a 2^19-byte output pitch on 4096 rows fits");
         // the same grid fits at E = 2 and not at E = 4 when the packed output row is what crosses the bound
         MapFrames e = {1u << 19, 4096u, 1u, 2u, 1ull << 19, 1ull << 20, 0, 0};
         CHECK(!map_plan(0x7f0000000000ull, e).fits32, "4288 rows of 2^20 bytes do not fit");
@@ -231,11 +129,6 @@ int main(int argc, char **argv)
         MapFrames g = {130u, 3u, 1u, 2u, 130, 260, 0, 0};
         CHECK(!map_plan(0x7f0000001000ull - 390, g).plan.p.fast && !map_plan(0x7f0000001000ull - 390, g).tail_ok, "tail over a page end");
         CHECK(map_plan(0x7f0000001000ull - 394, g).plan.p.fast, "tail inside the page");
-        // an interval that wraps 64 bits is representable (the caller refuses it by size)
-        const MapInterval big = map_interval(~0ull - 10, 100, 1, 100, 0, 1);
-        CHECK(big.hi > big.lo && big.hi - big.lo == 100, "128-bit interval");
-        const MapInterval tb = map_table_interval(~0ull - 10, 4);
-        CHECK(tb.hi > tb.lo && tb.hi - tb.lo == 1024, "128-bit table interval");
     }
     std::printf("%d cases, %d failures\n", cases, g_bad);
     return g_bad ? 1 : 0;

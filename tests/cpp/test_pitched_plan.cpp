@@ -12,39 +12,12 @@
 // Shapes include 1 x 1, one-row frames with absurd pitches, widths 1 ... 3 mod 4, sources whose span ends 1 ... 3 bytes before
 // a page end, pitches that push the offsets past 32 bits (metadata only: nothing here touches frame memory).
 // Usage: test_pitched_plan [cases] [seed]
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
 #include "../../rustyhgi_amd/csrc/hgi_pitched.h"
+#include "plan_test_util.h"
 
 using namespace hgi;
 
 namespace {
-
-uint64_t g_x = 0x9E3779B97F4A7C15ull;
-uint64_t rnd()
-{
-    g_x ^= g_x << 13;
-    g_x ^= g_x >> 7;
-    g_x ^= g_x << 17;
-    return g_x;
-}
-uint64_t rnd_in(uint64_t lo, uint64_t hi) { return lo + rnd() % (hi - lo + 1); }
-
-int g_bad = 0;
-#define CHECK(cond, ...)                                   \
-    do {                                                   \
-        if (!(cond)) {                                     \
-            if (g_bad < 20) {                              \
-                std::printf("FAIL %s: ", #cond);           \
-                std::printf(__VA_ARGS__);                  \
-                std::printf("\n");                         \
-            }                                              \
-            ++g_bad;                                       \
-        }                                                  \
-    } while (0)
 
 // fused_geom (hgi_fused_impl.h), 128 x 64 tiles, no row limit, restated for a packed batch
 struct Rule {
@@ -128,30 +101,7 @@ void one_case(int i)
         if (p.fast) CHECK((p.srec == sspan + 3) == r.tail, "case %d: packed frame: tail", i);
     }
     CHECK(p.nf == p.ipf * f.batch && p.nedge == (tpf - p.ipf) * f.batch && p.ipf == p.ix * p.iy, "case %d: totals", i);
-    // walk the launch
-    const uint64_t blocks = pitched_blocks(p);
-    CHECK(blocks == ((p.nedge + 7u) & ~7u) + p.nf, "case %d: blocks", i);
-    std::vector<uint8_t> seen((size_t)(tpf * f.batch), 0);
-    uint64_t idle = 0;
-    for (uint64_t b = 0; b < blocks; ++b) {
-        const PitchedTile t = pitched_tile(p, (uint32_t)b);
-        if (t.idle) {
-            CHECK(b >= p.nedge && b < ((p.nedge + 7u) & ~7u), "case %d: idle block %llu outside the padding", i, (unsigned long long)b);
-            ++idle;
-            continue;
-        }
-        CHECK(t.frame < f.batch && t.X0 % 128 == 0 && t.Y0 % 64 == 0 && t.X0 < f.width && t.Y0 < f.height,
-              "case %d: block %llu -> frame %u tile (%u, %u)", i, (unsigned long long)b, t.frame, t.X0, t.Y0);
-        if (!(t.frame < f.batch && t.X0 < f.width && t.Y0 < f.height)) continue;
-        const bool inside = (uint64_t)t.X0 + 128 <= f.width && (uint64_t)t.Y0 + 64 <= f.height;
-        if (!t.edge) CHECK(inside && p.fast, "case %d: interior block %llu is ragged", i, (unsigned long long)b);
-        if (t.edge && p.fast) CHECK(!inside, "case %d: ragged block %llu is interior", i, (unsigned long long)b);
-        uint8_t &s = seen[(size_t)(t.frame * tpf + (uint64_t)(t.Y0 / 64) * p.tx + t.X0 / 128)];
-        CHECK(s == 0, "case %d: tile covered twice", i);
-        s = 1;
-    }
-    CHECK(idle == ((p.nedge + 7u) & ~7u) - p.nedge, "case %d: %llu idle blocks", i, (unsigned long long)idle);
-    for (size_t k = 0; k < seen.size(); ++k) CHECK(seen[k] == 1, "case %d: tile %zu not covered", i, k);
+    walk_launch(i, p, f.width, f.height, f.batch, nullptr, 0);
 }
 
 }  // namespace

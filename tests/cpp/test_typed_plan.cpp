@@ -1,7 +1,6 @@
-// rustyhgi_amd/typed/hgi_typed_plan.h -- the two-sided plan of typed encode and its interval test -- on random shapes, pitches,
+// rustyhgi_amd/typed/hgi_typed_plan.h -- the two-sided plan of typed encode -- on random shapes, pitches,
 // strides, addresses, batches and element sizes:
-//   * every block of a launch walked through pitched_tile(): every tile of every frame covered exactly once, interior tiles with
-//     their body inside the image, idle blocks only in the padding behind the ragged tiles;
+//   * every block of a launch walked through pitched_tile() (walk_launch, plan_test_util.h);
 //   * `fast` against the documented rule evaluated here from scratch (include/hgi_typed.h): the image pitch and the grid pitch in
 //     BYTES within the 32-bit bound, and -- 2-byte elements of an odd width -- the two bytes behind the last image frame's span
 //     in the page of its last byte; fits32 / tail_ok say which half failed.  The GRID's address never enters: it is not read;
@@ -9,45 +8,14 @@
 //     the grid side's (Y0 + 63) * pitch + X0 + 128 for every block -- fits 32 bits when computed in 64; the write descriptor holds
 //     exactly the grid span, the read descriptor the image span plus 0 or 2 bytes; every element of every row a tile loads
 //     inside the image lies below the records;
-//   * the interval test against brute force: small layouts painted byte by byte into a map -- the image and the grid meet iff
-//     a byte of one lies between the first and the last byte of the other.
+// The byte intervals of the call, the page rule and the bound themselves are companion/hgi_sides.h's: test_sides.cpp.
 // Usage: test_typed_plan [cases] [seed]
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
 #include "../../rustyhgi_amd/typed/hgi_typed_plan.h"
+#include "plan_test_util.h"
 
 using namespace hgi;
 
 namespace {
-
-uint64_t g_x = 0x9E3779B97F4A7C15ull;
-uint64_t rnd()
-{
-    g_x ^= g_x << 13;
-    g_x ^= g_x >> 7;
-    g_x ^= g_x << 17;
-    return g_x;
-}
-uint64_t rnd_in(uint64_t lo, uint64_t hi) { return lo + rnd() % (hi - lo + 1); }
-
-int g_bad = 0;
-#define CHECK(cond, ...)                                   \
-    do {                                                   \
-        if (!(cond)) {                                     \
-            if (g_bad < 20) {                              \
-                std::printf("FAIL %s: ", #cond);           \
-                std::printf(__VA_ARGS__);                  \
-                std::printf("\n");                         \
-            }                                              \
-            ++g_bad;                                       \
-        }                                                  \
-    } while (0)
-
-// the header's rule for one side, restated
-bool side_fits(uint32_t h, uint64_t pitch) { return pitch < (1ull << 32) && ((uint64_t)h + 192) * pitch + 1024 < (1ull << 32); }
 
 void plan_case(int i)
 {
@@ -85,8 +53,7 @@ void plan_case(int i)
     if (!p.ok) return;
     CHECK(p.tx == (f.width + 127) / 128 && p.ty == (f.height + 63) / 64, "case %d: tiles %u x %u", i, p.tx, p.ty);
     CHECK(p.dp == gp && j.ip == ip && j.ispan == ispan, "case %d: pitches", i);
-    CHECK(typed_img_span(f.width, f.height, E, ip) == ispan, "case %d: image span", i);
-    CHECK(p.dstride == (f.batch > 1 ? f.grid_stride : 0) && r.istride == (f.batch > 1 ? f.img_stride : 0), "case %d: strides", i);
+    CHECK(p.dstride == (f.batch > 1 ? f.grid_stride : 0) && r.x.stride == (f.batch > 1 ? f.img_stride : 0), "case %d: strides", i);
     // the documented rule, from scratch
     const uint64_t end = src + (uint64_t)(f.batch - 1) * (f.batch > 1 ? f.img_stride : 0) + ispan;
     const bool fits = side_fits(f.height, gp) && side_fits(f.height, ip);
@@ -100,38 +67,22 @@ void plan_case(int i)
               (unsigned long long)ymax, (unsigned long long)gp);
         CHECK(ymax * ip + xmax * E < (1ull << 32), "case %d: image side: 32-bit offset overflow (%llu rows, pitch %llu)", i,
               (unsigned long long)ymax, (unsigned long long)ip);
-        CHECK(p.dp32 == gp && r.ip32 == ip, "case %d: 32-bit pitches", i);
+        CHECK(p.dp32 == gp && r.x.pitch32 == ip, "case %d: 32-bit pitches", i);
         CHECK(p.drec == gspan, "case %d: write records %u, span %llu", i, p.drec, (unsigned long long)gspan);
-        CHECK(r.irec == ispan + (E == 2 && f.width % 2 ? 2 : 0), "case %d: read records %u, span %llu", i, r.irec, (unsigned long long)ispan);
-        CHECK(ip % E == 0 && r.istride % E == 0 && src % E == 0, "case %d: whole elements", i);
+        CHECK(r.x.rec == ispan + (E == 2 && f.width % 2 ? 2 : 0), "case %d: read records %u, span %llu", i, r.x.rec, (unsigned long long)ispan);
+        CHECK(ip % E == 0 && r.x.stride % E == 0 && src % E == 0, "case %d: whole elements", i);
     } else {
         // a refused plan describes no buffer path on either side
-        CHECK(r.ip32 == 0 && r.irec == 0 && p.dp32 == 0 && p.drec == 0 && p.ix == 0 && p.iy == 0 && p.nf == 0,
+        CHECK(r.x.pitch32 == 0 && r.x.rec == 0 && p.dp32 == 0 && p.drec == 0 && p.ix == 0 && p.iy == 0 && p.nf == 0,
               "case %d: descriptors of a refused plan", i);
         return;     // nothing is launched
     }
     CHECK(p.nf == p.ipf * f.batch && p.nedge == (tpf - p.ipf) * f.batch && p.ipf == p.ix * p.iy, "case %d: totals", i);
     CHECK(p.ix == (f.width / 128) * (p.iy ? 1 : 0) && p.iy == (f.height / 64) * (p.ix ? 1 : 0), "case %d: interior %u x %u", i, p.ix, p.iy);
-    // walk the launch
-    const uint64_t blocks = pitched_blocks(p);
-    std::vector<uint8_t> seen((size_t)(tpf * f.batch), 0);
-    uint64_t idle = 0;
-    for (uint64_t b = 0; b < blocks; ++b) {
-        const PitchedTile t = pitched_tile(p, (uint32_t)b);
-        if (t.idle) {
-            CHECK(b >= p.nedge && b < ((p.nedge + 7u) & ~7u), "case %d: idle block %llu outside the padding", i, (unsigned long long)b);
-            ++idle;
-            continue;
-        }
-        CHECK(t.frame < f.batch && t.X0 % 128 == 0 && t.Y0 % 64 == 0 && t.X0 < f.width && t.Y0 < f.height,
-              "case %d: block %llu -> frame %u tile (%u, %u)", i, (unsigned long long)b, t.frame, t.X0, t.Y0);
-        if (!(t.frame < f.batch && t.X0 < f.width && t.Y0 < f.height)) continue;
-        const bool inside = (uint64_t)t.X0 + 128 <= f.width && (uint64_t)t.Y0 + 64 <= f.height;
-        CHECK(t.edge != inside, "case %d: block %llu: edge %d, body inside %d", i, (unsigned long long)b, (int)t.edge, (int)inside);
-        // the tile's origin on both sides, as the kernel forms it (32-bit arithmetic)
-        const uint32_t gbase = t.Y0 * p.dp32 + t.X0, ibase = t.Y0 * r.ip32 + t.X0 * E;
-        CHECK(gbase == (uint64_t)t.Y0 * gp + t.X0, "case %d: grid side: tile origin wraps", i);
-        CHECK(ibase == (uint64_t)t.Y0 * ip + (uint64_t)t.X0 * E, "case %d: image side: tile origin wraps", i);
+    // walk the launch: the tile's origin on both sides (bytes on the image side, pixels on the grid's)
+    const WalkSide sides[2] = {{"grid", p.dp32, gp, 1}, {"image", r.x.pitch32, ip, E}};
+    walk_launch(i, p, f.width, f.height, f.batch, sides, 2, [&](const PitchedTile &t, uint64_t b) {
+        const uint32_t gbase = t.Y0 * p.dp32 + t.X0, ibase = t.Y0 * r.x.pitch32 + t.X0 * E;
         // the last row of the tile inside the image, its last element on both sides: the offsets fit 32 bits and lie below
         // the records (the image side's b128 load that holds the last element may reach the two tail bytes, never further)
         const uint32_t ylast = (t.Y0 + 63 < f.height ? t.Y0 + 63 : f.height - 1) - t.Y0;
@@ -139,57 +90,13 @@ void plan_case(int i)
         const uint64_t glast = (uint64_t)gbase + (uint64_t)ylast * gp + xend, ilast = (uint64_t)ibase + (uint64_t)ylast * ip + (uint64_t)xend * E;
         CHECK(glast == (uint32_t)(gbase + ylast * p.dp32 + xend) && glast <= p.drec, "case %d: block %llu: last stored byte %llu, records %u", i,
               (unsigned long long)b, (unsigned long long)glast, p.drec);
-        CHECK(ilast == (uint32_t)(ibase + ylast * r.ip32 + xend * E) && ilast <= ispan, "case %d: block %llu: last loaded byte %llu, span %llu", i,
+        CHECK(ilast == (uint32_t)(ibase + ylast * r.x.pitch32 + xend * E) && ilast <= ispan, "case %d: block %llu: last loaded byte %llu, span %llu", i,
               (unsigned long long)b, (unsigned long long)ilast, (unsigned long long)ispan);
         // the dword that holds the last element of a row ends inside the records
         const uint64_t dw_end = ilast - E + 4 - ((ilast - E - ((uint64_t)ibase + (uint64_t)ylast * ip)) % 4);
-        CHECK(dw_end <= r.irec, "case %d: block %llu: the last element's dword ends at %llu, records %u", i, (unsigned long long)b,
-              (unsigned long long)dw_end, r.irec);
-        uint8_t &s = seen[(size_t)(t.frame * tpf + (uint64_t)(t.Y0 / 64) * p.tx + t.X0 / 128)];
-        CHECK(s == 0, "case %d: tile covered twice", i);
-        s = 1;
-    }
-    CHECK(idle == ((p.nedge + 7u) & ~7u) - p.nedge, "case %d: %llu idle blocks", i, (unsigned long long)idle);
-    for (size_t k = 0; k < seen.size(); ++k) CHECK(seen[k] == 1, "case %d: tile %zu not covered", i, k);
-}
-
-// The image and the grid somewhere in a 64-KiB arena; brute force: paint each one's conservative interval (first byte to last
-// byte) and compare with typed_meet.
-void interval_case(int i)
-{
-    const uint32_t N = 1u << 16;
-    const uint32_t w = (uint32_t)rnd_in(1, 40), h = (uint32_t)rnd_in(1, 12), batch = (uint32_t)rnd_in(1, 3), E = rnd() % 2 ? 2u : 4u;
-    TypedInterval iv[2];
-    std::vector<uint8_t> paint[2];
-    uint64_t prev_ptr = 0, prev_total = 1;
-    for (int k = 0; k < 2; ++k) {
-        const uint64_t row = k == 0 ? (uint64_t)w * E : w;
-        const uint64_t pitch = row + (k == 0 ? E : 1) * rnd_in(0, 30);
-        const uint64_t span = (uint64_t)(h - 1) * pitch + row;
-        const uint64_t stride = span + (k == 0 ? E : 1) * rnd_in(0, 50);
-        const uint64_t total = (uint64_t)(batch - 1) * stride + span;
-        // near or on one another every other case
-        uint64_t ptr = k && rnd() % 2 ? prev_ptr + rnd_in(0, 2 * prev_total) : rnd_in(0, N - total - 1);
-        if (ptr + total > N) ptr = N - total;
-        iv[k] = typed_interval(ptr, row, h, pitch, stride, batch);
-        paint[k].assign(N, 0);
-        uint64_t first = N, last = 0;
-        for (uint32_t b = 0; b < batch; ++b)
-            for (uint32_t y = 0; y < h; ++y)
-                for (uint64_t x = 0; x < row; ++x) {
-                    const uint64_t a = ptr + b * stride + y * pitch + x;
-                    first = a < first ? a : first;
-                    last = a > last ? a : last;
-                }
-        for (uint64_t a = first; a <= last; ++a) paint[k][a] = 1;
-        CHECK(iv[k].lo == first && iv[k].hi == last + 1, "interval %d side %d: [%llu, %llu) painted [%llu, %llu]", i, k,
-              (unsigned long long)iv[k].lo, (unsigned long long)iv[k].hi, (unsigned long long)first, (unsigned long long)last);
-        prev_ptr = ptr;
-        prev_total = total;
-    }
-    bool meet = false;
-    for (uint32_t j = 0; j < N && !meet; ++j) meet = paint[0][j] && paint[1][j];
-    CHECK(typed_meet(iv[0], iv[1]) == meet && typed_meet(iv[1], iv[0]) == meet, "interval %d: meet %d", i, (int)meet);
+        CHECK(dw_end <= r.x.rec, "case %d: block %llu: the last element's dword ends at %llu, records %u", i, (unsigned long long)b,
+              (unsigned long long)dw_end, r.x.rec);
+    });
 }
 
 }  // namespace
@@ -199,26 +106,25 @@ int main(int argc, char **argv)
     const int cases = argc > 1 ? std::atoi(argv[1]) : 300;
     if (argc > 2) g_x ^= std::strtoull(argv[2], nullptr, 0);
     for (int i = 0; i < cases; ++i) plan_case(i);
-    for (int i = 0; i < cases; ++i) interval_case(i);
     {
         // the image side alone pushes the offsets past 32 bits: refused, never narrowed (4096 elements of 4 bytes, 2^18 apart)
         TypedFrames f = {4096u, 4096u, 2u, 4u, 1ull << 20, 4096, 1ull << 32, 1ull << 24};
         const TypedJudged r = typed_plan(0x7f0000000000ull, f);
-        CHECK(r.plan.p.ok && !r.plan.p.fast && !r.fits32 && r.tail_ok && r.plan.ip32 == 0 && r.plan.irec == 0 && r.plan.p.dp32 == 0 &&
+        CHECK(r.plan.p.ok && !r.plan.p.fast && !r.fits32 && r.tail_ok && r.plan.x.pitch32 == 0 && r.plan.x.rec == 0 && r.plan.p.dp32 == 0 &&
                   r.plan.p.nf == 0, "a 2^20-byte image pitch on 4096 rows must be refused, on both sides");
         f.img_pitch = 1ull << 19;
         const TypedJudged q = typed_plan(0x7f0000000000ull, f);
-        CHECK(q.plan.p.fast && q.fits32 && q.plan.ip32 == (1u << 19), "a 2^19-byte image pitch on 4096 rows fits");
+        CHECK(q.plan.p.fast && q.fits32 && q.plan.x.pitch32 == (1u << 19), "a 2^19-byte image pitch on 4096 rows fits");
         // 2-byte elements, an odd width, the span of the last frame ending on the last byte of a page: two bytes more leave it
         TypedFrames g = {131u, 3u, 1u, 2u, 264, 131, 0, 0};
         const uint64_t span = 2 * 264 + 262;
         CHECK(!typed_plan(0x7f0000001000ull - span, g).plan.p.fast && !typed_plan(0x7f0000001000ull - span, g).tail_ok, "tail over a page end");
-        CHECK(typed_plan(0x7f0000001000ull - span - 2, g).plan.p.fast && typed_plan(0x7f0000001000ull - span - 2, g).plan.irec == span + 2,
+        CHECK(typed_plan(0x7f0000001000ull - span - 2, g).plan.p.fast && typed_plan(0x7f0000001000ull - span - 2, g).plan.x.rec == span + 2,
               "tail inside the page");
         CHECK(typed_plan(0x7f0000001000ull - span + 2, g).plan.p.fast, "tail at the start of the next page");
         g.elem = 4;      // 4-byte elements never read behind the span
         g.img_pitch = 528;
-        CHECK(typed_plan(0x7f0000001000ull - (2 * 528 + 524), g).plan.p.fast && typed_plan(0x7f0000001000ull - (2 * 528 + 524), g).plan.irec == 2 * 528 + 524,
+        CHECK(typed_plan(0x7f0000001000ull - (2 * 528 + 524), g).plan.p.fast && typed_plan(0x7f0000001000ull - (2 * 528 + 524), g).plan.x.rec == 2 * 528 + 524,
               "4-byte elements at a page end");
         g.elem = 2;      // an even width neither
         g.width = 130;
@@ -230,9 +136,6 @@ int main(int argc, char **argv)
             TypedFrames e = {w, 70u, 3u, 4u, 4ull * w + 12, w + 5, 70ull * (4 * w + 12), 70ull * (w + 5) + 1};
             for (uint64_t a = 0; a < 4096; a += 4) CHECK(typed_plan(0x7f0000000000ull + a, e).plan.p.fast, "width %u at image address +%llu", w, (unsigned long long)a);
         }
-        // an interval that wraps 64 bits is representable (the caller refuses it by size)
-        const TypedInterval big = typed_interval(~0ull - 10, 100, 1, 100, 0, 1);
-        CHECK(big.hi > big.lo && big.hi - big.lo == 100, "128-bit interval");
     }
     std::printf("%d cases, %d failures\n", cases, g_bad);
     return g_bad ? 1 : 0;

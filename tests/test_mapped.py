@@ -13,6 +13,7 @@ import sys
 import numpy as np
 import pytest
 
+import companion_layer as CL
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -53,12 +54,8 @@ def test_library_exports_exactly_the_three_entry_points(M):
     assert strings, "binutils strings is needed to search the object for switch names"
     text = subprocess.check_output([strings, M.LIB_PATH], text=True)
     assert re.findall(r"HGI_[A-Z0-9_]+", text) == []
-    for fn in sorted(os.listdir(MAP_DIR)):
-        if os.path.isfile(os.path.join(MAP_DIR, fn)):
-            src = open(os.path.join(MAP_DIR, fn)).read()
-            assert "getenv(" not in src and "KNOBS_ENV" not in src and "HGI_KNOB(" not in src, fn
-            assert "hipMalloc" not in src and "hgi_ctx" not in src, fn      # no device allocation, no ctx
-    mk = open(os.path.join(MAP_DIR, "Makefile")).read()
+    CL.check_sources(MAP_DIR, ["Makefile", "hgi_fused_map_dec.hip", "hgi_map.hip", "hgi_map.map", "hgi_map_kernels.h", "hgi_map_plan.h"])
+    mk = CL.makefile(MAP_DIR, "map", "hgi_fused_dec.hip")
     assert "-fvisibility=hidden" in mk and "-lhgi_hip" not in mk and "--version-script=hgi_map.map" in mk
     for dep in re.findall(r'#include "(?:\.\./csrc/)?(hgi_[\w.]+)"', open(os.path.join(ROOT, "rustyhgi_amd", "csrc", "hgi_fused_impl.h")).read()):
         assert "$(CSRC)/" + dep in mk, dep + " is included by the tile procedure and missing from the Makefile's dependencies"
@@ -246,7 +243,9 @@ def test_dynamic_lds_is_the_decoders_plus_the_table_and_the_staging_rows():
     src = open(os.path.join(MAP_DIR, "hgi_fused_map_dec.hip")).read()
     assert "lds_for_waves((size_t)buf_bytes(nh) + 256 * (size_t)elem + kMapStageBytes, waves)" in src and "kMapStageBytes = 2 * TW * (NL / CH)" in src
     assert "u8 *tab = smem + buf_bytes(nh);" in src and "const_cast<u8 *>(tab) + 256 * E + 2 * TW * (lane >> LCH)" in src
-    assert "hipFuncGetAttributes" in src and "sharedSizeBytes == 0" in src
+    entry = open(os.path.join(CL.COMPANION_DIR, "hgi_entry.h")).read()      # the launcher's check, shared by the four units
+    assert "static_lds_is_empty(reinterpret_cast" in src and '#include "../companion/hgi_entry.h"' in src
+    assert "hipFuncGetAttributes" in entry and "sharedSizeBytes == 0" in entry
     assert '#include "../csrc/hgi_fused_dec.hip"' in src and '#include "../csrc/hgi_fused_pitched.h"' in src
     assert "#define HGI_FUSED_NO_LAUNCHERS 1" in src
 

@@ -13,6 +13,7 @@ import sys
 import numpy as np
 import pytest
 
+import companion_layer as CL
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -52,12 +53,11 @@ def test_library_exports_exactly_the_three_entry_points(R):
     if strings:
         text = subprocess.check_output([strings, R.LIB_PATH], text=True)
         assert re.findall(r"HGI_[A-Z0-9_]+", text) == []
-    for fn in sorted(os.listdir(RECON_DIR)):
-        if os.path.isfile(os.path.join(RECON_DIR, fn)):
-            src = open(os.path.join(RECON_DIR, fn)).read()
-            assert "getenv(" not in src and "KNOBS_ENV" not in src, fn
-    mk = open(os.path.join(RECON_DIR, "Makefile")).read()
+    CL.check_sources(RECON_DIR, ["Makefile", "hgi_fused_recon_enc.hip", "hgi_recon.hip", "hgi_recon.map", "hgi_recon_kernels.h", "hgi_recon_plan.h"])
+    mk = CL.makefile(RECON_DIR, "recon", "hgi_fused_enc.hip")
     assert "-fvisibility=hidden" in mk and "-lhgi_hip" not in mk and "--version-script=hgi_recon.map" in mk
+    for dep in re.findall(r'#include "(?:\.\./csrc/)?(hgi_[\w.]+)"', open(os.path.join(ROOT, "rustyhgi_amd", "csrc", "hgi_fused_impl.h")).read()):
+        assert "$(CSRC)/" + dep in mk, dep + " is included by the tile procedure and missing from the Makefile's dependencies"
     readelf = shutil.which("readelf")
     if readelf:
         assert "libhgi_hip" not in subprocess.check_output([readelf, "-d", R.LIB_PATH], text=True)
@@ -199,7 +199,9 @@ def test_recon_unit_is_the_sdwa_build_within_the_encoder_budget(tmp_path):
 def test_dynamic_lds_is_the_uniform_encoders():
     src = open(os.path.join(RECON_DIR, "hgi_fused_recon_enc.hip")).read()
     assert "(size_t)buf_bytes(nh) + ((rbuf_bytes(nh) + 15) & ~15) + 256" in src
-    assert "hipFuncGetAttributes" in src and "sharedSizeBytes == 0" in src
+    entry = open(os.path.join(CL.COMPANION_DIR, "hgi_entry.h")).read()      # the launcher's check, shared by the four units
+    assert "static_lds_is_empty(reinterpret_cast" in src and '#include "../companion/hgi_entry.h"' in src
+    assert "hipFuncGetAttributes" in entry and "sharedSizeBytes == 0" in entry
     assert '#include "../csrc/hgi_fused_enc.hip"' in src and '#include "../csrc/hgi_fused_pitched.h"' in src
     assert "#define HGI_FUSED_NO_LAUNCHERS 1" in src
 

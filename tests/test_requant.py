@@ -18,6 +18,7 @@ import pytest
 
 import geometry_designs as G
 import operand_designs as D
+import companion_layer as CL
 from conftest import ROOT, SEED0
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -59,14 +60,8 @@ def test_library_exports_exactly_the_three_entry_points(Q):
     assert strings, "binutils strings is needed to search the object for switch names"
     text = subprocess.check_output([strings, Q.LIB_PATH], text=True)
     assert re.findall(r"HGI_[A-Z0-9_]+", text) == []
-    assert sorted(f for f in os.listdir(REQUANT_DIR) if os.path.isfile(os.path.join(REQUANT_DIR, f))) == \
-        ["Makefile", "hgi_fused_requant.hip", "hgi_requant.hip", "hgi_requant.map", "hgi_requant_kernels.h", "hgi_requant_plan.h"]
-    for fn in sorted(os.listdir(REQUANT_DIR)):
-        if os.path.isfile(os.path.join(REQUANT_DIR, fn)):
-            src = open(os.path.join(REQUANT_DIR, fn)).read()
-            assert "getenv" not in src and "KNOBS_ENV" not in src and "HGI_KNOB(" not in src, fn
-            assert "hipMalloc" not in src and "hgi_ctx" not in src, fn      # no device allocation, no ctx
-    mk = open(os.path.join(REQUANT_DIR, "Makefile")).read()
+    CL.check_sources(REQUANT_DIR, ["Makefile", "hgi_fused_requant.hip", "hgi_requant.hip", "hgi_requant.map", "hgi_requant_kernels.h", "hgi_requant_plan.h"])
+    mk = CL.makefile(REQUANT_DIR, "requant", "hgi_fused_enc.hip")
     assert "-fvisibility=hidden" in mk and "-lhgi_hip" not in mk and "--version-script=hgi_requant.map" in mk
     for dep in re.findall(r'#include "(?:\.\./csrc/)?(hgi_[\w.]+)"', open(os.path.join(ROOT, "rustyhgi_amd", "csrc", "hgi_fused_impl.h")).read()):
         assert "$(CSRC)/" + dep in mk, dep + " is included by the tile procedure and missing from the Makefile's dependencies"
@@ -74,8 +69,9 @@ def test_library_exports_exactly_the_three_entry_points(Q):
         assert "$(CSRC)/" + dep in mk, dep
     # the same compiler flags as the three sibling libraries
     flags = re.search(r"^CXXFLAGS \?= (.*)$", mk, flags=re.M).group(1)
-    for sib in ("recon", "map", "typed"):
-        assert re.search(r"^CXXFLAGS \?= (.*)$", open(os.path.join(ROOT, "rustyhgi_amd", sib, "Makefile")).read(), flags=re.M).group(1) == flags, sib
+    for sib, fused in (("recon", "hgi_fused_enc.hip"), ("map", "hgi_fused_dec.hip"), ("typed", "hgi_fused_enc.hip")):
+        sib_mk = CL.makefile(os.path.join(ROOT, "rustyhgi_amd", sib), sib, fused)      # (no flags of its own: the fragment's)
+        assert [m for m in re.findall(r"^CXXFLAGS \?= (.*)$", sib_mk, flags=re.M)] == [flags], sib
     readelf = shutil.which("readelf")
     assert readelf, "binutils readelf is needed to list what the library links"
     assert "libhgi_hip" not in subprocess.check_output([readelf, "-d", Q.LIB_PATH], text=True)
@@ -238,7 +234,9 @@ def test_requant_unit_is_within_the_encoder_budget(tmp_path):
     assert "amdgpu_waves_per_eu(HGI_ENC_WAVES_PER_EU)" in src
     assert '#include "../csrc/hgi_fused_enc.hip"' in src and '#include "../csrc/hgi_fused_pitched.h"' in src
     assert "#define HGI_FUSED_NO_LAUNCHERS 1" in src
-    assert "hipFuncGetAttributes" in src and "sharedSizeBytes == 0" in src
+    entry = open(os.path.join(CL.COMPANION_DIR, "hgi_entry.h")).read()      # the launcher's check, shared by the four units
+    assert "static_lds_is_empty(reinterpret_cast" in src and '#include "../companion/hgi_entry.h"' in src
+    assert "hipFuncGetAttributes" in entry and "sharedSizeBytes == 0" in entry
     assert "(size_t)buf_bytes(nh) + ((rbuf_bytes(nh) + 15) & ~15) + 256" in src      # the uniform encoder's dynamic LDS, nothing added
 
 

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import typed_reference as TR
+import companion_layer as CL
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -57,14 +58,8 @@ def test_library_exports_exactly_the_three_entry_points(T):
     assert strings, "binutils strings is needed to search the object for switch names"
     text = subprocess.check_output([strings, T.LIB_PATH], text=True)
     assert re.findall(r"HGI_[A-Z0-9_]+", text) == []
-    assert sorted(f for f in os.listdir(TYPED_DIR) if os.path.isfile(os.path.join(TYPED_DIR, f))) == \
-        ["Makefile", "hgi_fused_typed_enc.hip", "hgi_typed.hip", "hgi_typed.map", "hgi_typed_kernels.h", "hgi_typed_plan.h"]
-    for fn in sorted(os.listdir(TYPED_DIR)):
-        if os.path.isfile(os.path.join(TYPED_DIR, fn)):
-            src = open(os.path.join(TYPED_DIR, fn)).read()
-            assert "getenv(" not in src and "KNOBS_ENV" not in src and "HGI_KNOB(" not in src, fn
-            assert "hipMalloc" not in src and "hgi_ctx" not in src, fn      # no device allocation, no ctx
-    mk = open(os.path.join(TYPED_DIR, "Makefile")).read()
+    CL.check_sources(TYPED_DIR, ["Makefile", "hgi_fused_typed_enc.hip", "hgi_typed.hip", "hgi_typed.map", "hgi_typed_kernels.h", "hgi_typed_plan.h"])
+    mk = CL.makefile(TYPED_DIR, "typed", "hgi_fused_enc.hip")
     assert "-fvisibility=hidden" in mk and "-lhgi_hip" not in mk and "--version-script=hgi_typed.map" in mk
     for dep in re.findall(r'#include "(?:\.\./csrc/)?(hgi_[\w.]+)"', open(os.path.join(ROOT, "rustyhgi_amd", "csrc", "hgi_fused_impl.h")).read()):
         assert "$(CSRC)/" + dep in mk, dep + " is included by the tile procedure and missing from the Makefile's dependencies"
@@ -254,7 +249,9 @@ def test_typed_unit_is_within_its_budgets(tmp_path):
     assert "amdgpu_waves_per_eu(kTypedWavesPerEu)" in src
     assert '#include "../csrc/hgi_fused_enc.hip"' in src and '#include "../csrc/hgi_fused_pitched.h"' in src
     assert "#define HGI_FUSED_NO_LAUNCHERS 1" in src
-    assert "hipFuncGetAttributes" in src and "sharedSizeBytes == 0" in src
+    entry = open(os.path.join(CL.COMPANION_DIR, "hgi_entry.h")).read()      # the launcher's check, shared by the four units
+    assert "static_lds_is_empty(reinterpret_cast" in src and '#include "../companion/hgi_entry.h"' in src
+    assert "hipFuncGetAttributes" in entry and "sharedSizeBytes == 0" in entry
     assert "(size_t)buf_bytes(nh) + ((rbuf_bytes(nh) + 15) & ~15) + 256" in src      # the uniform encoder's dynamic LDS, nothing added
 
 
