@@ -18,7 +18,7 @@
 #include "../csrc/hgi_fused_dec.hip"   // the decode direction's build settings and tile procedure, 128 x 64 tiles
 #include "../csrc/hgi_fused_pitched.h"
 #pragma clang diagnostic pop
-#include "../companion/hgi_entry.h"
+#include "../companion/hgi_tile.h"
 #include "hgi_map_kernels.h"
 
 // Resident tiles per CU of a launch of 8 192 tiles and more (the dynamic LDS is padded to that: lds_for_waves).  The start is
@@ -43,12 +43,6 @@ namespace {
 
 // Staging rows of the finest pass: the two decoded rows of each of the NL / CH row pairs a wave works on at a time, 128 B each.
 constexpr int kMapStageBytes = 2 * TW * (NL / CH);
-
-// The output's side of a tile: descriptor over one frame's span, byte pitch, offset of the tile's origin Y0 * pitch + X0 * E.
-struct MapOut {
-    __amdgpu_buffer_rsrc_t rd;
-    u32 P, base;
-};
 
 // Sixteen decoded pixels (four packed dwords) -> their table entries, E pieces of 16 B.  All lookups are issued before the
 // first result is used: one dependent LDS round trip for the lookups (the exchange in front of them is a second one).  E = 4: ds_read_b32; E = 2: ds_read_u16, two
@@ -144,7 +138,7 @@ __device__ __forceinline__ v4u map_row_pixels(const u8 *row, int c)
 
 // The finest level of dec_fine_fast -- the same arithmetic on the same registers -- then the lookups and the E-byte row stores.
 template <int INTERP, int E, int EDGE>
-__device__ __forceinline__ void dec_fine_map(const u8 *buf, const u8 *tab, const MapOut &mo, const v4u (&odd)[NFINE], int rows, int cols)
+__device__ __forceinline__ void dec_fine_map(const u8 *buf, const u8 *tab, const TileSide &mo, const v4u (&odd)[NFINE], int rows, int cols)
 {
     const int lane = HGI_LANE, c8 = lane & (CH - 1);
     u8 *stg = const_cast<u8 *>(tab) + 256 * E + 2 * TW * (lane >> LCH);      // the lane's two staging rows, behind the table
@@ -152,7 +146,7 @@ __device__ __forceinline__ void dec_fine_map(const u8 *buf, const u8 *tab, const
     const bool last = (lane & (CH - 1)) == CH - 1;
     const u8 *r0 = buf + rp0 * S + 16 * (lane & (CH - 1));
     const u8 *h0 = buf + HCOL + rp0;
-    const u32 P = __builtin_amdgcn_readfirstlane(mo.P);
+    const u32 P = __builtin_amdgcn_readfirstlane(mo.pitch);
     u32 voff = mo.base + 2 * rp0 * P + 16 * c8;
 #pragma unroll
     for (int it = 0; it < NFINE; ++it, r0 += (NL / CH) * S, h0 += NL / CH, voff += 2 * (NL / CH) * P) {
@@ -164,27 +158,13 @@ __device__ __forceinline__ void dec_fine_map(const u8 *buf, const u8 *tab, const
         const u32 he = h0[0], hf = h0[1];
         e16 = last ? he : e16;
         f16 = last ? hf : f16;
-        uint2 c, fl;
-        c.x = __builtin_amdgcn_perm(E_.y, E_.x, 0x06040200u);
-        c.y = __builtin_amdgcn_perm(E_.w, E_.z, 0x06040200u);
-        fl.x = __builtin_amdgcn_perm(F.y, F.x, 0x06040200u);
-        fl.y = __builtin_amdgcn_perm(F.w, F.z, 0x06040200u);
-        u32 P0, P1;
-        pred8<INTERP>(c, e16, fl, f16, P0, P1);
-        u32 e0 = E_.x, e1 = E_.y, e2 = E_.z, e3 = E_.w, o0 = O.x, o1 = O.y, o2 = O.z, o3 = O.w;
-        // row y: odd columns;  cell j of the lane = byte j of P0 (j < 4) or byte j-4 of P1
-        HGI_ADDB(e0, 1, P0, 0); HGI_ADDB(e0, 3, P0, 1); HGI_ADDB(e1, 1, P0, 2); HGI_ADDB(e1, 3, P0, 3);
-        HGI_ADDB(e2, 1, P1, 0); HGI_ADDB(e2, 3, P1, 1); HGI_ADDB(e3, 1, P1, 2); HGI_ADDB(e3, 3, P1, 3);
-        // row y+1: every column
-        HGI_ADDB(o0, 0, P0, 0); HGI_ADDB(o0, 1, P0, 0); HGI_ADDB(o0, 2, P0, 1); HGI_ADDB(o0, 3, P0, 1);
-        HGI_ADDB(o1, 0, P0, 2); HGI_ADDB(o1, 1, P0, 2); HGI_ADDB(o1, 2, P0, 3); HGI_ADDB(o1, 3, P0, 3);
-        HGI_ADDB(o2, 0, P1, 0); HGI_ADDB(o2, 1, P1, 0); HGI_ADDB(o2, 2, P1, 1); HGI_ADDB(o2, 3, P1, 1);
-        HGI_ADDB(o3, 0, P1, 2); HGI_ADDB(o3, 1, P1, 2); HGI_ADDB(o3, 2, P1, 3); HGI_ADDB(o3, 3, P1, 3);
+        v4u r0v, r1v;
+        dec_fine_rows<INTERP>(E_, F, e16, f16, O, r0v, r1v);
         // 16 px x 2 rows as packed bytes -> the staging rows of the lane's row pair; back come the pixels of the lane's pieces
         // (dword k of `px` = piece k at E = 4, half of piece k / 2 at E = 2: map_lookup's order), then every lookup of the task,
         // then the packing, then the stores
-        *reinterpret_cast<v4u *>(stg + 16 * c8) = v4u{e0, e1, e2, e3};
-        *reinterpret_cast<v4u *>(stg + TW + 16 * c8) = v4u{o0, o1, o2, o3};
+        *reinterpret_cast<v4u *>(stg + 16 * c8) = r0v;
+        *reinterpret_cast<v4u *>(stg + TW + 16 * c8) = r1v;
         LDS_ORDER();
         const v4u pa = map_row_pixels<E>(stg, c8), pb = map_row_pixels<E>(stg + TW, c8);
         LDS_ORDER();
@@ -192,33 +172,17 @@ __device__ __forceinline__ void dec_fine_map(const u8 *buf, const u8 *tab, const
         map_lookup<E>(tab, pa, a);
         map_lookup<E>(tab, pb, b);
         const int y = 2 * (rp0 + it * (NL / CH));
-        store_map_rows<E, EDGE>(a, b, mo.rd, voff, P, cols * E - 16 * c8, y < rows, y + 1 < rows);
+        store_map_rows<E, EDGE>(a, b, mo.r, voff, P, cols * E - 16 * c8, y < rows, y + 1 < rows);
     }
 }
 
 // dec_tile_fast / dec_tile_edge's level chain, then the mapped finest level.  EDGE == 0: the tile body lies inside the image;
 // 1: full width inside, even height (no column logic, the range check drops the rows below the image); 2: any ragged tile.
 template <int INTERP, int E, int EDGE>
-__device__ __forceinline__ void dec_tile_map(u8 *buf, const u8 *tab, Tile tl, const MapOut &mo, const v4u (&odd)[NFINE], u32 k, u32 W, u32 H)
+__device__ __forceinline__ void dec_tile_map(u8 *buf, const u8 *tab, Tile tl, const TileSide &mo, const v4u (&odd)[NFINE], u32 k, u32 W, u32 H)
 {
-    const int rows = (int)(H - tl.Y0), cols = (int)(W - tl.X0);
-#define HGI_DEC_MAP_COARSE(SUB)                                    \
-    if (k > HGI_LOG2(SUB)) {                                       \
-        dec_cells<INTERP, EDGE != 0>(buf, SUB, tl, W, H);          \
-        dec_halo_cells<INTERP>(buf, SUB, tl, W, H);                \
-        LDS_ORDER();                                               \
-    }
-    if (MAXK >= 6) HGI_DEC_MAP_COARSE(32)
-    if (MAXK >= 5) HGI_DEC_MAP_COARSE(16)
-    HGI_DEC_MAP_COARSE(8)
-    HGI_DEC_MAP_COARSE(4)
-#undef HGI_DEC_MAP_COARSE
-    if (k >= 2) {
-        dec_level2_fast<INTERP, EDGE>(buf, rows, cols);
-        dec_halo_cells<INTERP>(buf, 2, tl, W, H);
-        LDS_ORDER();
-    }
-    dec_fine_map<INTERP, E, EDGE>(buf, tab, mo, odd, rows, cols);
+    dec_chain<INTERP, EDGE>(buf, tl, k, W, H);
+    dec_fine_map<INTERP, E, EDGE>(buf, tab, mo, odd, (int)(H - tl.Y0), (int)(W - tl.X0));
 }
 
 // A lane's 4 * E bytes of the table: one vector load, at any alignment of the table.
@@ -253,10 +217,7 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(map_waves_pe
     // 32-bit buffer offsets on both sides (the host launches nothing else)
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(fr), 0, p.srec, 0x00020000);
     const u32 rb = __builtin_amdgcn_readfirstlane(tl.Y0 * p.sp32 + tl.X0);
-    MapOut mo;
-    mo.rd = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(out), 0, mp.x.rec, 0x00020000);
-    mo.P = mp.x.pitch32;
-    mo.base = __builtin_amdgcn_readfirstlane(tl.Y0 * mp.x.pitch32 + tl.X0 * (u32)E);
+    const TileSide mo = tile_side(mp.x, out, tl, E);
     SeedRegs seeds;
     ConeLane cone;
     Stage st;
@@ -295,11 +256,8 @@ hipError_t launch_decode_map(const uint8_t *grid, const void *table, void *out, 
                              uint32_t up, int interp, hipStream_t s)
 {
     const PitchedPlan &p = mp.p;
-    if (k < 1 || k > (u32)MAXK || !p.ok || !p.fast || (elem != 2 && elem != 4)) return hipErrorInvalidValue;
-    const bool cone = up != 0;
-    if (cone && (k != 4 || up > (u32)kConeMaxUp)) return hipErrorInvalidValue;
-    const Seeds sd = {nullptr, nullptr, 0, 0, 0, up};
-    const int nh = k >= 2 ? (int)k : 1;
+    const TileLaunch t = tile_launch(p, k, up);
+    if (!t.ok || (elem != 2 && elem != 4)) return hipErrorInvalidValue;
     // resident tiles per CU: launch_decode_pitched's policy on this launch's tile count, unless this unit was built with a
     // number of its own
     const u64 tiles = (u64)p.nf + p.nedge;
@@ -308,34 +266,17 @@ hipError_t launch_decode_map(const uint8_t *grid, const void *table, void *out, 
         waves = 0;
     else if (HGI_MAP_WAVES > 0)
         waves = HGI_MAP_WAVES;
-    else if (!cone)
+    else if (!t.cone)
         waves = p.W > 4096 || k > 4 ? HGI_DEC_STREAM_WAVES_WIDE : k == 1 ? HGI_DEC_STREAM_WAVES_L1 : HGI_DEC_STREAM_WAVES;
     else
         waves = tiles >= 65536 ? HGI_DEC_DEEP_WAVES : HGI_DEC_SHALLOW_WAVES;
-    const size_t lds = lds_for_waves((size_t)buf_bytes(nh) + 256 * (size_t)elem + kMapStageBytes, waves);   // the decoder's, the table and the staging rows behind it
-    const dim3 blocks((u32)pitched_blocks(p)), b(NL);
+    const size_t lds = lds_for_waves((size_t)buf_bytes(t.nh) + 256 * (size_t)elem + kMapStageBytes, waves);   // the decoder's, the table and the staging rows behind it
     const u8 *tab = static_cast<const u8 *>(table);
     u8 *dst = static_cast<u8 *>(out);
-    // the table's place is counted from LDS offset 0: checked once per instantiation on the host
-#define HGI_MAP(I, SE, EL)                                                                                            \
-    do {                                                                                                              \
-        static const hipError_t lds0 = static_lds_is_empty(reinterpret_cast<const void *>(&k_dec_map<I, SE, EL>));    \
-        if (lds0 != hipSuccess) return lds0;                                                                          \
-        hipLaunchKernelGGL((k_dec_map<I, SE, EL>), blocks, b, lds, s, grid, tab, dst, k, sd, mp);                     \
-    } while (0)
-#define HGI_MAP_SE(I, SE)                                          \
-    do {                                                           \
-        if (elem == 4) HGI_MAP(I, SE, 4); else HGI_MAP(I, SE, 2);  \
-    } while (0)
-#define HGI_MAP_I(I)                                               \
-    do {                                                           \
-        if (cone) HGI_MAP_SE(I, 2); else HGI_MAP_SE(I, 0);         \
-    } while (0)
-    if (interp == kInterpCrossed) HGI_MAP_I(kInterpCrossed); else HGI_MAP_I(kInterpLeftTop);
-#undef HGI_MAP_I
-#undef HGI_MAP_SE
-#undef HGI_MAP
-    return hipGetLastError();
+    return with_choices(
+        [&](auto I, auto SE, auto EL) { return launch_tile_kernel<k_dec_map<I, SE, EL>>(t, lds, s, grid, tab, dst, k, t.sd, mp); },
+        OneOf<kInterpCrossed, kInterpLeftTop>{interp == kInterpCrossed ? kInterpCrossed : kInterpLeftTop}, OneOf<2, 0>{t.cone ? 2 : 0},
+        OneOf<4, 2>{(int)elem});
 }
 
 }  // namespace hgi

@@ -15,23 +15,17 @@
 #include "../csrc/hgi_fused_enc.hip"   // the encode direction's build settings and tile procedure, 128 x 64 tiles
 #include "../csrc/hgi_fused_pitched.h"
 #pragma clang diagnostic pop
-#include "../companion/hgi_entry.h"
+#include "../companion/hgi_tile.h"
 #include "hgi_recon_kernels.h"
 
 namespace hgi {
 namespace {
 
-// The reconstruction's side of a tile: Buf's `rd`, `W` and `base` once more.
-struct ReconOut {
-    __amdgpu_buffer_rsrc_t rd;
-    u32 W, base;                 // write pitch, Y0 * pitch + X0
-};
-
 // enc_fine_fast with the reconstruction: same lane map, same loads, same grid stores; per task eight packed adds, eight byte
 // permutes and one more row pair stored.  A task's grid rows are stored before its reconstruction rows are formed, so the
 // two row pairs are not live together for longer than the adds take.
 template <int INTERP, bool IDENT, int EDGE = 0>
-__device__ __forceinline__ void enc_fine_recon(const u8 *buf, const u8 *rbuf, const u8 *slut, const Buf &b, const ReconOut &ro,
+__device__ __forceinline__ void enc_fine_recon(const u8 *buf, const u8 *rbuf, const u8 *slut, const Buf &b, const TileSide &ro,
                                                const v4u (&odd)[NFINE], int rows = TH, int cols = TW)
 {
     const int lane = HGI_LANE;
@@ -41,8 +35,8 @@ __device__ __forceinline__ void enc_fine_recon(const u8 *buf, const u8 *rbuf, co
     const u8 *c0 = rbuf + rp0 * S2 + 8 * (lane & (CH - 1));
     const u8 *h0 = rbuf + RCOL + rp0;
     u32 voff = b.base + 2 * rp0 * b.W + 16 * (lane & (CH - 1));
-    u32 roff = ro.base + 2 * rp0 * ro.W + 16 * (lane & (CH - 1));
-    const u32 Ws = __builtin_amdgcn_readfirstlane(b.W), Wr = __builtin_amdgcn_readfirstlane(ro.W);
+    u32 roff = ro.base + 2 * rp0 * ro.pitch + 16 * (lane & (CH - 1));
+    const u32 Ws = __builtin_amdgcn_readfirstlane(b.W), Wr = __builtin_amdgcn_readfirstlane(ro.pitch);
     constexpr int NIT = NFINE, PAIR = NFINE >= 2 ? 2 : 1;   // row-pair groups per LDS dependency chain (enc_fine_fast's batch)
     static_assert(NIT % PAIR == 0, "fine level iterations come in pairs");
 #pragma unroll
@@ -107,9 +101,9 @@ __device__ __forceinline__ void enc_fine_recon(const u8 *buf, const u8 *rbuf, co
                 q1 = v4u{add4(g0, pp0), add4(g1, pp1), add4(g2, pp2), add4(g3, pp3)};
             }
             if (EDGE == 2)
-                store_rows_edge(q0, q1, ro.rd, vr, Wr, nvalid, y < rows, y + 1 < rows);
+                store_rows_edge(q0, q1, ro.r, vr, Wr, nvalid, y < rows, y + 1 < rows);
             else
-                store_row_pair(q0, q1, ro.rd, vr, Wr);
+                store_row_pair(q0, q1, ro.r, vr, Wr);
         }
         r0 += PAIR * (NL / CH) * S;
         c0 += PAIR * (NL / CH) * S2;
@@ -121,7 +115,7 @@ __device__ __forceinline__ void enc_fine_recon(const u8 *buf, const u8 *rbuf, co
 
 // enc_tile_edge's chain with the new last link
 template <int INTERP, bool IDENT, int EDGE>
-__device__ __forceinline__ void enc_tile_edge_recon(u8 *buf, u8 *rbuf, const u8 *slut, const TileCtx &cur, const ReconOut &ro,
+__device__ __forceinline__ void enc_tile_edge_recon(u8 *buf, u8 *rbuf, const u8 *slut, const TileCtx &cur, const TileSide &ro,
                                                     const v4u (&odd)[NFINE], u32 k, u32 W, u32 H)
 {
 #define HGI_ENC_EDGE_COARSE(SUB)                                                   \
@@ -144,7 +138,7 @@ __device__ __forceinline__ void enc_tile_edge_recon(u8 *buf, u8 *rbuf, const u8 
 
 // enc_tile_fast's chain with the new last link
 template <int INTERP, bool IDENT>
-__device__ __forceinline__ void enc_tile_fast_recon(u8 *buf, u8 *rbuf, const u8 *slut, const TileCtx &cur, const ReconOut &ro,
+__device__ __forceinline__ void enc_tile_fast_recon(u8 *buf, u8 *rbuf, const u8 *slut, const TileCtx &cur, const TileSide &ro,
                                                     const v4u (&odd)[NFINE], u32 k, u32 W, u32 H)
 {
 #define HGI_ENC_COARSE(SUB)                                                                    \
@@ -190,10 +184,7 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(IDENT ? HGI_
     // 32-bit buffer offsets on all three sides (the host launches nothing else)
     u32 rb;
     TileCtx cur = {tl, pitched_buf(fr, out, p, tl, &rb)};
-    ReconOut ro;
-    ro.rd = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(rout), 0, rp.x.rec, 0x00020000);
-    ro.W = rp.x.pitch32;
-    ro.base = __builtin_amdgcn_readfirstlane(tl.Y0 * rp.x.pitch32 + tl.X0);
+    const TileSide ro = tile_side(rp.x, rout, tl, 1);
     Stage st;
     if (!edge) {
         pitched_issue<false>(st, cur.b.rs, rb, p.sp32, W, tl, (int)k, nh);
@@ -227,33 +218,14 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(IDENT ? HGI_
 hipError_t launch_encode_recon(const uint8_t *img, uint8_t *grid, uint8_t *recon, const ReconPlan &rp, uint32_t k, uint32_t up,
                                int interp, const Lut256 &lut, bool ident, hipStream_t s)
 {
-    if (k < 1 || k > (u32)MAXK || !rp.p.ok || !rp.p.fast) return hipErrorInvalidValue;
-    const bool cone = up != 0;
-    if (cone && (k != 4 || up > (u32)kConeMaxUp)) return hipErrorInvalidValue;
-    const Seeds sd = {nullptr, nullptr, 0, 0, 0, up};
-    const int nh = k >= 2 ? (int)k : 1;
-    const size_t lds = (size_t)buf_bytes(nh) + ((rbuf_bytes(nh) + 15) & ~15) + 256;   // the uniform encoder's
-    const dim3 blocks((u32)pitched_blocks(rp.p)), b(NL);
-    // lut_at() addresses the table from LDS offset 0: checked once per instantiation on the host
-#define HGI_REC(I, ID, SE)                                                                                             \
-    do {                                                                                                               \
-        static const hipError_t lds0 = static_lds_is_empty(reinterpret_cast<const void *>(&k_enc_recon<I, ID, SE>));   \
-        if (lds0 != hipSuccess) return lds0;                                                                           \
-        hipLaunchKernelGGL((k_enc_recon<I, ID, SE>), blocks, b, lds, s, img, grid, recon, k, lut, sd, rp);             \
-    } while (0)
-#define HGI_REC_ID(I, ID)                                          \
-    do {                                                           \
-        if (cone) HGI_REC(I, ID, 2); else HGI_REC(I, ID, 0);       \
-    } while (0)
-#define HGI_REC_I(I)                                               \
-    do {                                                           \
-        if (ident) HGI_REC_ID(I, true); else HGI_REC_ID(I, false); \
-    } while (0)
-    if (interp == kInterpCrossed) HGI_REC_I(kInterpCrossed); else HGI_REC_I(kInterpLeftTop);
-#undef HGI_REC_I
-#undef HGI_REC_ID
-#undef HGI_REC
-    return hipGetLastError();
+    const TileLaunch t = tile_launch(rp.p, k, up);
+    if (!t.ok) return hipErrorInvalidValue;
+    return with_choices(
+        [&](auto I, auto ID, auto SE) {
+            return launch_tile_kernel<k_enc_recon<I, ID != 0, SE>>(t, enc_lds_bytes(t.nh), s, img, grid, recon, k, lut, t.sd, rp);
+        },
+        OneOf<kInterpCrossed, kInterpLeftTop>{interp == kInterpCrossed ? kInterpCrossed : kInterpLeftTop}, OneOf<1, 0>{ident ? 1 : 0},
+        OneOf<2, 0>{t.cone ? 2 : 0});
 }
 
 }  // namespace hgi

@@ -23,7 +23,7 @@
 #include "../csrc/hgi_fused_enc.hip"   // the encode direction's build settings and tile procedure, 128 x 64 tiles
 #include "../csrc/hgi_fused_pitched.h"
 #pragma clang diagnostic pop
-#include "../companion/hgi_entry.h"
+#include "../companion/hgi_tile.h"
 #include "hgi_requant_kernels.h"
 
 namespace hgi {
@@ -77,23 +77,8 @@ __device__ __forceinline__ void dec_fine_keep(u8 *buf, v4u (&odd)[NFINE], int ro
         const u32 he = h0[0], hf = h0[1];
         e16 = last ? he : e16;
         f16 = last ? hf : f16;
-        uint2 c, fl;
-        c.x = __builtin_amdgcn_perm(E.y, E.x, 0x06040200u);
-        c.y = __builtin_amdgcn_perm(E.w, E.z, 0x06040200u);
-        fl.x = __builtin_amdgcn_perm(F.y, F.x, 0x06040200u);
-        fl.y = __builtin_amdgcn_perm(F.w, F.z, 0x06040200u);
-        u32 P0, P1;
-        pred8<INTERP>(c, e16, fl, f16, P0, P1);
-        u32 e0 = E.x, e1 = E.y, e2 = E.z, e3 = E.w, o0 = O.x, o1 = O.y, o2 = O.z, o3 = O.w;
-        // row y: odd columns;  cell j of the lane = byte j of P0 (j < 4) or byte j-4 of P1
-        HGI_ADDB(e0, 1, P0, 0); HGI_ADDB(e0, 3, P0, 1); HGI_ADDB(e1, 1, P0, 2); HGI_ADDB(e1, 3, P0, 3);
-        HGI_ADDB(e2, 1, P1, 0); HGI_ADDB(e2, 3, P1, 1); HGI_ADDB(e3, 1, P1, 2); HGI_ADDB(e3, 3, P1, 3);
-        // row y+1: every column
-        HGI_ADDB(o0, 0, P0, 0); HGI_ADDB(o0, 1, P0, 0); HGI_ADDB(o0, 2, P0, 1); HGI_ADDB(o0, 3, P0, 1);
-        HGI_ADDB(o1, 0, P0, 2); HGI_ADDB(o1, 1, P0, 2); HGI_ADDB(o1, 2, P0, 3); HGI_ADDB(o1, 3, P0, 3);
-        HGI_ADDB(o2, 0, P1, 0); HGI_ADDB(o2, 1, P1, 0); HGI_ADDB(o2, 2, P1, 1); HGI_ADDB(o2, 3, P1, 1);
-        HGI_ADDB(o3, 0, P1, 2); HGI_ADDB(o3, 1, P1, 2); HGI_ADDB(o3, 2, P1, 3); HGI_ADDB(o3, 3, P1, 3);
-        v4u r0v = {e0, e1, e2, e3}, r1v = {o0, o1, o2, o3};
+        v4u r0v, r1v;
+        dec_fine_rows<INTERP>(E, F, e16, f16, O, r0v, r1v);
         if (EDGE == 2) {
             const int y = 2 * (rp0 + it * (NL / CH));
             r0v &= cm;
@@ -104,51 +89,6 @@ __device__ __forceinline__ void dec_fine_keep(u8 *buf, v4u (&odd)[NFINE], int ro
             *reinterpret_cast<v4u *>(r0) = r0v;
         }
         odd[it] = r1v;
-    }
-}
-
-// The decoder's levels sub = 2^(k-1) ... 2 of an interior tile, in place (dec_tile_fast's chain without its finest pass)
-template <int INTERP>
-__device__ __forceinline__ void dec_chain_fast(u8 *buf, Tile tl, u32 k, u32 W, u32 H)
-{
-#define HGI_RQ_DEC_COARSE(SUB)                                 \
-    if (k > HGI_LOG2(SUB)) {                                   \
-        dec_cells<INTERP, false>(buf, SUB, tl, W, H);          \
-        dec_halo_cells<INTERP>(buf, SUB, tl, W, H);            \
-        LDS_ORDER();                                           \
-    }
-    if (MAXK >= 6) HGI_RQ_DEC_COARSE(32)
-    if (MAXK >= 5) HGI_RQ_DEC_COARSE(16)
-    HGI_RQ_DEC_COARSE(8)
-    HGI_RQ_DEC_COARSE(4)
-#undef HGI_RQ_DEC_COARSE
-    if (k >= 2) {
-        dec_level2_fast<INTERP>(buf);
-        dec_halo_cells<INTERP>(buf, 2, tl, W, H);
-        LDS_ORDER();
-    }
-}
-
-// ... and of a ragged tile (dec_tile_edge's chain without its finest pass)
-template <int INTERP, int EDGE>
-__device__ __forceinline__ void dec_chain_edge(u8 *buf, Tile tl, u32 k, u32 W, u32 H)
-{
-    const int rows = (int)(H - tl.Y0), cols = (int)(W - tl.X0);
-#define HGI_RQ_DEC_EDGE_COARSE(SUB)                            \
-    if (k > HGI_LOG2(SUB)) {                                   \
-        dec_cells<INTERP, true>(buf, SUB, tl, W, H);           \
-        dec_halo_cells<INTERP>(buf, SUB, tl, W, H);            \
-        LDS_ORDER();                                           \
-    }
-    if (MAXK >= 6) HGI_RQ_DEC_EDGE_COARSE(32)
-    if (MAXK >= 5) HGI_RQ_DEC_EDGE_COARSE(16)
-    HGI_RQ_DEC_EDGE_COARSE(8)
-    HGI_RQ_DEC_EDGE_COARSE(4)
-#undef HGI_RQ_DEC_EDGE_COARSE
-    if (k >= 2) {
-        dec_level2_fast<INTERP, EDGE>(buf, rows, cols);
-        dec_halo_cells<INTERP>(buf, 2, tl, W, H);
-        LDS_ORDER();
     }
 }
 
@@ -206,7 +146,7 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(HGI_ENC_WAVE
             LDS_ORDER();
             dec_seed_commit(buf, seeds, k);
         }
-        dec_chain_fast<INTERP>(buf, tl, k, W, H);
+        dec_chain<INTERP, 0>(buf, tl, k, W, H);
         lattice_fast(buf, rbuf, nh);
         dec_fine_keep<INTERP>(buf, st.o);
         LDS_ORDER();
@@ -228,7 +168,7 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(HGI_ENC_WAVE
     }
     const int rows = (int)(H - tl.Y0), cols = (int)(W - tl.X0);
     if (tl.X0 + TW <= W && !(H & 1u)) {
-        dec_chain_edge<INTERP, 1>(buf, tl, k, W, H);
+        dec_chain<INTERP, 1>(buf, tl, k, W, H);
         lattice_fast(buf, rbuf, nh);
         dec_fine_keep<INTERP, 1>(buf, st.o, rows, cols);
         LDS_ORDER();
@@ -236,7 +176,7 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(HGI_ENC_WAVE
         enc_seed_commit<SEEDED>(buf, rbuf, seeds, k);
         enc_tile_edge<INTERP, false, 1>(buf, rbuf, slut, cur, st.o, k, W, H);
     } else {
-        dec_chain_edge<INTERP, 2>(buf, tl, k, W, H);
+        dec_chain<INTERP, 2>(buf, tl, k, W, H);
         lattice_fast(buf, rbuf, nh);
         dec_fine_keep<INTERP, 2>(buf, st.o, rows, cols);
         LDS_ORDER();
@@ -251,28 +191,11 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(HGI_ENC_WAVE
 hipError_t launch_requant(const uint8_t *src, uint8_t *dst, const PitchedPlan &p, uint32_t k, uint32_t up, int interp,
                           const Lut256 &lut, hipStream_t s)
 {
-    if (k < 1 || k > (u32)MAXK || !p.ok || !p.fast) return hipErrorInvalidValue;
-    const bool cone = up != 0;
-    if (cone && (k != 4 || up > (u32)kConeMaxUp)) return hipErrorInvalidValue;
-    const Seeds sd = {nullptr, nullptr, 0, 0, 0, up};
-    const int nh = k >= 2 ? (int)k : 1;
-    const size_t lds = (size_t)buf_bytes(nh) + ((rbuf_bytes(nh) + 15) & ~15) + 256;   // the uniform encoder's
-    const dim3 blocks((u32)pitched_blocks(p)), b(NL);
-    // lut_at() addresses the table from LDS offset 0: checked once per instantiation on the host
-#define HGI_RQ(I, SE)                                                                                                \
-    do {                                                                                                             \
-        static const hipError_t lds0 = static_lds_is_empty(reinterpret_cast<const void *>(&k_requant<I, SE>));       \
-        if (lds0 != hipSuccess) return lds0;                                                                         \
-        hipLaunchKernelGGL((k_requant<I, SE>), blocks, b, lds, s, src, dst, k, lut, sd, p);                          \
-    } while (0)
-#define HGI_RQ_I(I)                                  \
-    do {                                             \
-        if (cone) HGI_RQ(I, 2); else HGI_RQ(I, 0);   \
-    } while (0)
-    if (interp == kInterpCrossed) HGI_RQ_I(kInterpCrossed); else HGI_RQ_I(kInterpLeftTop);
-#undef HGI_RQ_I
-#undef HGI_RQ
-    return hipGetLastError();
+    const TileLaunch t = tile_launch(p, k, up);
+    if (!t.ok) return hipErrorInvalidValue;
+    return with_choices(
+        [&](auto I, auto SE) { return launch_tile_kernel<k_requant<I, SE>>(t, enc_lds_bytes(t.nh), s, src, dst, k, lut, t.sd, p); },
+        OneOf<kInterpCrossed, kInterpLeftTop>{interp == kInterpCrossed ? kInterpCrossed : kInterpLeftTop}, OneOf<2, 0>{t.cone ? 2 : 0});
 }
 
 }  // namespace hgi

@@ -30,7 +30,7 @@
 #include "../csrc/hgi_fused_enc.hip"   // the encode direction's build settings and tile procedure, 128 x 64 tiles
 #include "../csrc/hgi_fused_pitched.h"
 #pragma clang diagnostic pop
-#include "../companion/hgi_entry.h"
+#include "../companion/hgi_tile.h"
 #include "hgi_typed_kernels.h"
 
 namespace hgi {
@@ -413,40 +413,16 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(kTypedWavesP
 hipError_t launch_encode_typed(const void *img, uint8_t *grid, const TypedPlan &tp, uint32_t elem, bool bf16, float scale, float bias,
                                uint32_t k, uint32_t up, int interp, const Lut256 &lut, bool ident, hipStream_t s)
 {
-    if (k < 1 || k > (u32)MAXK || !tp.p.ok || !tp.p.fast || (elem != 2 && elem != 4) || (bf16 && elem != 2)) return hipErrorInvalidValue;
-    const bool cone = up != 0;
-    if (cone && (k != 4 || up > (u32)kConeMaxUp)) return hipErrorInvalidValue;
-    const Seeds sd = {nullptr, nullptr, 0, 0, 0, up};
+    const TileLaunch t = tile_launch(tp.p, k, up);
+    if (!t.ok || (elem != 2 && elem != 4) || (bf16 && elem != 2)) return hipErrorInvalidValue;
     const Cvt cv = {scale, bias, bf16 ? 1u : 0u};
     const u8 *src = static_cast<const u8 *>(img);
-    const int nh = k >= 2 ? (int)k : 1;
-    const size_t lds = (size_t)buf_bytes(nh) + ((rbuf_bytes(nh) + 15) & ~15) + 256;   // the uniform encoder's
-    const dim3 blocks((u32)pitched_blocks(tp.p)), b(NL);
-    // lut_at() addresses the table from LDS offset 0: checked once per instantiation on the host
-#define HGI_TYP(I, ID, SE, EL)                                                                                               \
-    do {                                                                                                                     \
-        static const hipError_t lds0 = static_lds_is_empty(reinterpret_cast<const void *>(&k_enc_typed<I, ID, SE, EL>));     \
-        if (lds0 != hipSuccess) return lds0;                                                                                 \
-        hipLaunchKernelGGL((k_enc_typed<I, ID, SE, EL>), blocks, b, lds, s, src, grid, k, lut, sd, tp, cv);                  \
-    } while (0)
-#define HGI_TYP_SE(I, ID, SE)                                          \
-    do {                                                               \
-        if (elem == 4) HGI_TYP(I, ID, SE, 4); else HGI_TYP(I, ID, SE, 2); \
-    } while (0)
-#define HGI_TYP_ID(I, ID)                                              \
-    do {                                                               \
-        if (cone) HGI_TYP_SE(I, ID, 2); else HGI_TYP_SE(I, ID, 0);     \
-    } while (0)
-#define HGI_TYP_I(I)                                                   \
-    do {                                                               \
-        if (ident) HGI_TYP_ID(I, true); else HGI_TYP_ID(I, false);     \
-    } while (0)
-    if (interp == kInterpCrossed) HGI_TYP_I(kInterpCrossed); else HGI_TYP_I(kInterpLeftTop);
-#undef HGI_TYP_I
-#undef HGI_TYP_ID
-#undef HGI_TYP_SE
-#undef HGI_TYP
-    return hipGetLastError();
+    return with_choices(
+        [&](auto I, auto ID, auto SE, auto EL) {
+            return launch_tile_kernel<k_enc_typed<I, ID != 0, SE, EL>>(t, enc_lds_bytes(t.nh), s, src, grid, k, lut, t.sd, tp, cv);
+        },
+        OneOf<kInterpCrossed, kInterpLeftTop>{interp == kInterpCrossed ? kInterpCrossed : kInterpLeftTop}, OneOf<1, 0>{ident ? 1 : 0},
+        OneOf<2, 0>{t.cone ? 2 : 0}, OneOf<4, 2>{(int)elem});
 }
 
 }  // namespace hgi

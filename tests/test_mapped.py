@@ -24,16 +24,11 @@ NAMES = ("hgi_map_decode_dev", "hgi_map_last_error", "hgi_map_version")
 
 @pytest.fixture(scope="module")
 def M():
-    """The binding, with the library built first if it is missing."""
-    from rustyhgi_amd import _ffi_map
-    if not os.path.exists(_ffi_map.LIB_PATH):
-        subprocess.check_call(["make", "-s", "-C", MAP_DIR, "-j4", "all"])
-    _ffi_map.lib()
-    return _ffi_map
+    return CL.binding("map")
 
 
 def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hgi_map.h")).read(), flags=re.S)
+    return CL.header("map")
 
 
 def test_library_exports_exactly_the_three_entry_points(M):
@@ -89,12 +84,6 @@ def test_ctypes_table_matches_the_header(M):
     # the header takes hgi_status / hgi_interp from hgi.h and declares no type of its own
     assert '#include "hgi.h"' in open(os.path.join(ROOT, "include", "hgi_map.h")).read()
     assert not re.search(r"\b(typedef|struct|enum)\b", _header())
-
-
-def _page_aligned(n):
-    raw = np.zeros(n + 8192, np.uint8)
-    off = (-raw.ctypes.data) % 4096
-    return raw, raw.ctypes.data + off
 
 
 def test_c_abi_refuses_bad_arguments_without_a_device(M):
@@ -154,7 +143,7 @@ def test_c_abi_refuses_bad_arguments_without_a_device(M):
     # the same byte pitch is what counts: 2^24 elements of 4 bytes are refused, of 2 bytes served as far as the rules go
     assert call(grid=1 << 50, out=2 << 50, table=3 << 50, elem=4, op=4 << 24) == U
     # width % 4 != 0 and the span's last byte at offset 4095 of its page: the three tail bytes leave the page (a synthetic address)
-    raw, page = _page_aligned(3 * 4096)
+    raw, page = CL.page_aligned(3 * 4096)
     w, h, gp = 30, 8, 40
     span = (h - 1) * gp + w
     assert call(grid=page + 4096 - span, w=w) == U and b"tail" in err() and b"4-KiB" in err()
@@ -176,24 +165,7 @@ def test_c_abi_refuses_bad_arguments_without_a_device(M):
 
 def test_entry_point_decides_every_rule_before_the_first_hip_call():
     """hgi_map.hip: in the entry point no HIP call stands before the launch, and the launch stands behind the last refusal."""
-    src = open(os.path.join(MAP_DIR, "hgi_map.hip")).read()
-    body = src[src.index("hgi_status hgi_map_decode_dev("):src.index("const char *hgi_map_last_error")]
-    first_hip = min(m.start() for m in re.finditer(r"\bhip[A-Z]\w*\s*\(|launch_decode_map\s*\(", body))
-    assert body[first_hip:].startswith("launch_decode_map(")
-    assert "return fail(HGI_EINVAL" not in body[first_hip:] and "return fail(HGI_EUNSUPPORTED" not in body[first_hip:]
-    assert body.index("return HGI_OK;") < body.index("return fail(")      # the empty call is decided first
-    # every HGI_EINVAL rule stands before the first HGI_EUNSUPPORTED one
-    assert max(m.start() for m in re.finditer(r"fail\(HGI_EINVAL", body)) < min(m.start() for m in re.finditer(r"fail\(HGI_EUNSUPPORTED", body))
-
-
-def _isa(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path / "hgi_fused_map_dec.s")
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S",
-                           os.path.join(MAP_DIR, "hgi_fused_map_dec.hip"), "-o", out], stderr=subprocess.DEVNULL)
-    return out
+    CL.check_rule_order("map", "hgi_map_decode_dev", "launch_decode_map")
 
 
 @pytest.mark.timeout(900)
@@ -204,7 +176,7 @@ def test_map_unit_is_within_its_budgets(tmp_path):
     declares -- DESIGN.md 4.11: E = 4 at the decoder's 8 (64), E = 2 at 7 (72), the cone two fewer (80 / 96).  The uniform and
     pitched kernels stay in their own units."""
     import check_isa
-    path = _isa(tmp_path)
+    path = CL.isa("map", tmp_path)
     r = check_isa.check(path)
     assert r["kernels"] == 8, r
     assert r["partial_writes"] > 400, r
@@ -216,11 +188,7 @@ def test_map_unit_is_within_its_budgets(tmp_path):
     # the lookups are LDS reads of the element size, the wide stores nt
     assert "ds_read_b32" in text and "ds_read_u16" in text
     assert re.search(r"buffer_store_dwordx4 .* nt", text)
-    res = {}
-    for m in re.finditer(r"\.group_segment_fixed_size:\s*(\d+).*?\.name:\s*(\S+).*?\.private_segment_fixed_size:\s*(\d+).*?\.vgpr_count:\s*(\d+)",
-                         text, flags=re.S):
-        if "k_dec_map" in m.group(2):
-            res[m.group(2)] = (int(m.group(4)), int(m.group(1)), int(m.group(3)))
+    res = CL.resources(text, "k_dec_map")
     assert len(res) == 8, res
     # 512 VGPRs per SIMD lane, allocated in eights: waves w -> at most (512 / w) rounded down to a multiple of 8
     budget = {(0, 4): 64, (0, 2): 72, (2, 4): 80, (2, 2): 96}      # (SEEDED, E) -> 8, 7, 6, 5 waves per SIMD
@@ -240,25 +208,16 @@ def test_map_unit_is_within_its_budgets(tmp_path):
 def test_dynamic_lds_is_the_decoders_plus_the_table_and_the_staging_rows():
     """The decoder's own layout first (no offset of the included procedure moves), the 256 * E bytes of the table behind it, then
     the 2 KiB of staging rows through which the lanes of a row exchange pixels; no static LDS."""
-    src = open(os.path.join(MAP_DIR, "hgi_fused_map_dec.hip")).read()
-    assert "lds_for_waves((size_t)buf_bytes(nh) + 256 * (size_t)elem + kMapStageBytes, waves)" in src and "kMapStageBytes = 2 * TW * (NL / CH)" in src
+    src = CL.unit_source("map", "hgi_fused_dec.hip")
+    assert "lds_for_waves((size_t)buf_bytes(t.nh) + 256 * (size_t)elem + kMapStageBytes, waves)" in src and "kMapStageBytes = 2 * TW * (NL / CH)" in src
     assert "u8 *tab = smem + buf_bytes(nh);" in src and "const_cast<u8 *>(tab) + 256 * E + 2 * TW * (lane >> LCH)" in src
-    entry = open(os.path.join(CL.COMPANION_DIR, "hgi_entry.h")).read()      # the launcher's check, shared by the four units
-    assert "static_lds_is_empty(reinterpret_cast" in src and '#include "../companion/hgi_entry.h"' in src
-    assert "hipFuncGetAttributes" in entry and "sharedSizeBytes == 0" in entry
-    assert '#include "../csrc/hgi_fused_dec.hip"' in src and '#include "../csrc/hgi_fused_pitched.h"' in src
-    assert "#define HGI_FUSED_NO_LAUNCHERS 1" in src
 
 
 def test_plan_and_intervals_under_asan_ubsan(tmp_path):
     """tests/cpp/test_map_plan.cpp, a stand-alone program: random shapes, pitches, alignments, batches and element sizes; every
     block walked through the map, every 32-bit offset of both sides bounded against the records, the fits, tail and interval
     rules against brute force."""
-    exe = str(tmp_path / "test_map_plan")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", os.path.join(ROOT, "tests", "cpp", "test_map_plan.cpp"), "-o", exe])
-    p = subprocess.run([exe, "1500", "0x48474939"], capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0 and "1500 cases, 0 failures" in p.stdout, p.stdout[-3000:] + p.stderr[-3000:]
+    CL.run_plan_program("map", tmp_path)
 
 
 def _decoder():
@@ -371,7 +330,4 @@ def test_affine_table_is_the_float32_arithmetic_it_says():
 
 
 def test_build_entry_builds_the_companion_library():
-    src = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert '"rustyhgi_amd", "map"' in src
-    assert src.index('"rustyhgi_amd", "recon"') < src.index('"rustyhgi_amd", "map"')
-    assert "rustyhgi_amd/map/_obj*/" in open(os.path.join(ROOT, ".gitignore")).read()
+    CL.check_build_entry("map", after="recon")

@@ -24,16 +24,11 @@ NAMES = ("hgi_recon_encode_u8_dev", "hgi_recon_last_error", "hgi_recon_version")
 
 @pytest.fixture(scope="module")
 def R():
-    """The binding, with the library built first if it is missing."""
-    from rustyhgi_amd import _ffi_recon
-    if not os.path.exists(_ffi_recon.LIB_PATH):
-        subprocess.check_call(["make", "-s", "-C", RECON_DIR, "-j4", "all"])
-    _ffi_recon.lib()
-    return _ffi_recon
+    return CL.binding("recon")
 
 
 def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hgi_recon.h")).read(), flags=re.S)
+    return CL.header("recon")
 
 
 def test_library_exports_exactly_the_three_entry_points(R):
@@ -89,12 +84,6 @@ def test_ctypes_table_matches_the_header(R):
     assert not re.search(r"\b(typedef|struct|enum)\b", _header())
 
 
-def _page_aligned(n):
-    raw = np.zeros(n + 8192, np.uint8)
-    off = (-raw.ctypes.data) % 4096
-    return raw, raw.ctypes.data + off
-
-
 def test_c_abi_refuses_bad_arguments_without_a_device(R):
     """Every HGI_EINVAL / HGI_EUNSUPPORTED rule of include/hgi_recon.h, decided before the first HIP call: the buffers here are
     host memory (or plain numbers where the shape is too large to exist) and are never touched."""
@@ -141,7 +130,7 @@ def test_c_abi_refuses_bad_arguments_without_a_device(R):
     for side in ("sp", "dp", "rp"):      # (8 + 192) * 2^25 >= 2^32 on one side at a time (numbers only)
         assert call(src=1 << 50, dst=2 << 50, rec=3 << 50, **{side: 1 << 25}) == U and b"32-bit" in err(), side
     # width % 4 != 0 and the span's last byte at offset 4095 of its page: the three tail bytes leave the page
-    raw, page = _page_aligned(3 * 4096)
+    raw, page = CL.page_aligned(3 * 4096)
     w, h, sp = 30, 8, 40
     span = (h - 1) * sp + w
     assert call(src=page + 4096 - span, w=w, rp=36) == U and b"tail" in err() and b"4-KiB" in err()
@@ -158,16 +147,6 @@ def test_c_abi_refuses_bad_arguments_without_a_device(R):
     assert (a == 0).all() and (o == 0).all() and (r == 0).all() and (raw == 0).all()
 
 
-def _isa(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path / "hgi_fused_recon_enc.s")
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S",
-                           os.path.join(RECON_DIR, "hgi_fused_recon_enc.hip"), "-o", out], stderr=subprocess.DEVNULL)
-    return out
-
-
 @pytest.mark.timeout(900)
 def test_recon_unit_is_the_sdwa_build_within_the_encoder_budget(tmp_path):
     """k_enc_recon<interp, ident, unseeded | cone>: eight kernels, the SDWA quantizer really there, the hazard rules of
@@ -175,7 +154,7 @@ def test_recon_unit_is_the_sdwa_build_within_the_encoder_budget(tmp_path):
     scratch, no spills, no DPP, no traps, no static LDS (the table sits at LDS offset 0), at most 128 VGPRs -- and, what DESIGN.md
     4.10 records, within the 102 of five waves per SIMD.  The uniform and pitched kernels stay in their own units."""
     import check_isa
-    path = _isa(tmp_path)
+    path = CL.isa("recon", tmp_path)
     r = check_isa.check(path)
     assert r["kernels"] == 8, r
     assert r["partial_writes"] > 400, r
@@ -184,11 +163,7 @@ def test_recon_unit_is_the_sdwa_build_within_the_encoder_budget(tmp_path):
     text = open(path).read()
     assert len(set(re.findall(r"\b(_Z\w*k_enc_recon\w*):", text))) == 8
     assert "k_enc_tiles" not in text and "k_enc_pitched" not in text
-    res = {}
-    for m in re.finditer(r"\.group_segment_fixed_size:\s*(\d+).*?\.name:\s*(\S+).*?\.private_segment_fixed_size:\s*(\d+).*?\.vgpr_count:\s*(\d+)",
-                         text, flags=re.S):
-        if "k_enc_recon" in m.group(2):
-            res[m.group(2)] = (int(m.group(4)), int(m.group(1)), int(m.group(3)))
+    res = CL.resources(text, "k_enc_recon")
     assert len(res) == 8, res
     for k, (vgprs, lds, scratch) in res.items():
         assert lds == 0 and scratch == 0, (k, lds, scratch)
@@ -197,23 +172,16 @@ def test_recon_unit_is_the_sdwa_build_within_the_encoder_budget(tmp_path):
 
 
 def test_dynamic_lds_is_the_uniform_encoders():
-    src = open(os.path.join(RECON_DIR, "hgi_fused_recon_enc.hip")).read()
-    assert "(size_t)buf_bytes(nh) + ((rbuf_bytes(nh) + 15) & ~15) + 256" in src
-    entry = open(os.path.join(CL.COMPANION_DIR, "hgi_entry.h")).read()      # the launcher's check, shared by the four units
-    assert "static_lds_is_empty(reinterpret_cast" in src and '#include "../companion/hgi_entry.h"' in src
-    assert "hipFuncGetAttributes" in entry and "sharedSizeBytes == 0" in entry
-    assert '#include "../csrc/hgi_fused_enc.hip"' in src and '#include "../csrc/hgi_fused_pitched.h"' in src
-    assert "#define HGI_FUSED_NO_LAUNCHERS 1" in src
+    """The formula stands once, in companion/hgi_tile.h; the unit's launcher calls it, and the kernel lays the table, `buf` and
+    `rbuf` out as the uniform encoder does."""
+    src = CL.unit_source("recon", "hgi_fused_enc.hip")
+    assert "u8 *buf = smem + 256 - HCOL;" in src and "u8 *rbuf = smem + 256 + buf_bytes(nh) - RCOL;" in src
 
 
 def test_plan_and_intervals_under_asan_ubsan(tmp_path):
     """tests/cpp/test_recon_plan.cpp, a stand-alone program: random shapes, pitches, alignments and batches; every block walked
     through the map, every 32-bit offset of all three sides bounded, the `fast` rule and the interval tests against brute force."""
-    exe = str(tmp_path / "test_recon_plan")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", os.path.join(ROOT, "tests", "cpp", "test_recon_plan.cpp"), "-o", exe])
-    p = subprocess.run([exe, "1500", "0x48474939"], capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0 and "1500 cases, 0 failures" in p.stdout, p.stdout[-3000:] + p.stderr[-3000:]
+    CL.run_plan_program("recon", tmp_path)
 
 
 def _encoder():
@@ -281,6 +249,4 @@ def test_python_mirror_refuses_bad_views_before_any_device_call(R):
 
 
 def test_build_entry_builds_the_companion_library():
-    src = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert '"rustyhgi_amd", "recon"' in src
-    assert "rustyhgi_amd/recon/_obj*/" in open(os.path.join(ROOT, ".gitignore")).read()
+    CL.check_build_entry("recon")

@@ -29,16 +29,11 @@ NAMES = ("hgi_requant_dev", "hgi_requant_last_error", "hgi_requant_version")
 
 @pytest.fixture(scope="module")
 def Q():
-    """The binding, with the library built first if it is missing."""
-    from rustyhgi_amd import _ffi_requant
-    if not os.path.exists(_ffi_requant.LIB_PATH):
-        subprocess.check_call(["make", "-s", "-C", REQUANT_DIR, "-j4", "all"])
-    _ffi_requant.lib()
-    return _ffi_requant
+    return CL.binding("requant")
 
 
 def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hgi_requant.h")).read(), flags=re.S)
+    return CL.header("requant")
 
 
 # ------------------------------------------------------------------------------------------------- exports and build
@@ -107,12 +102,6 @@ def test_ctypes_table_matches_the_header(Q):
 
 
 # ---------------------------------------------------------------------------------------------------- argument rules
-def _page_aligned(n):
-    raw = np.zeros(n + 8192, np.uint8)
-    off = (-raw.ctypes.data) % 4096
-    return raw, raw.ctypes.data + off
-
-
 def test_c_abi_refuses_bad_arguments_without_a_device(Q):
     """Every HGI_EINVAL / HGI_EUNSUPPORTED rule of include/hgi_requant.h, decided before the first HIP call: the buffers here
     are host memory (or plain numbers where the shape is too large to exist) and are never touched."""
@@ -156,7 +145,7 @@ def test_c_abi_refuses_bad_arguments_without_a_device(Q):
         assert call(src=1 << 50, dst=2 << 50, **{side: 1 << 25}) == U and b"32-bit" in err(), side
     assert call(lut=I) == U and b"identity" in err() and b"copy the source" in err()
     # width % 4 != 0 and the span's last byte at offset 4095 of its page: the three tail bytes leave the page
-    raw, page = _page_aligned(3 * 4096)
+    raw, page = CL.page_aligned(3 * 4096)
     w, h, sp = 30, 8, 40
     span = (h - 1) * sp + w
     assert call(src=page + 4096 - span, w=w) == U and b"tail" in err() and b"4-KiB" in err()
@@ -178,26 +167,10 @@ def test_c_abi_refuses_bad_arguments_without_a_device(Q):
 def test_entry_point_decides_every_rule_before_the_first_hip_call():
     """hgi_requant.hip: in the entry point no HIP call stands before the launch, the launch stands behind the last refusal, and
     every HGI_EINVAL rule stands before the first HGI_EUNSUPPORTED one."""
-    src = open(os.path.join(REQUANT_DIR, "hgi_requant.hip")).read()
-    body = src[src.index("hgi_status hgi_requant_dev("):src.index("const char *hgi_requant_last_error")]
-    first_hip = min(m.start() for m in re.finditer(r"\bhip[A-Z]\w*\s*\(|launch_requant\s*\(", body))
-    assert body[first_hip:].startswith("launch_requant(")
-    assert "return fail(HGI_EINVAL" not in body[first_hip:] and "return fail(HGI_EUNSUPPORTED" not in body[first_hip:]
-    assert body.index("return HGI_OK;") < body.index("return fail(")      # the empty call is decided first
-    assert max(m.start() for m in re.finditer(r"fail\(HGI_EINVAL", body)) < min(m.start() for m in re.finditer(r"fail\(HGI_EUNSUPPORTED", body))
+    CL.check_rule_order("requant", "hgi_requant_dev", "launch_requant")
 
 
 # ------------------------------------------------------------------------------------------------------ kernel unit
-def _isa(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path / "hgi_fused_requant.s")
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S",
-                           os.path.join(REQUANT_DIR, "hgi_fused_requant.hip"), "-o", out], stderr=subprocess.DEVNULL)
-    return out
-
-
 @pytest.mark.timeout(900)
 def test_requant_unit_is_within_the_encoder_budget(tmp_path):
     """k_requant<interp, unseeded | cone>: four kernels and no other -- none for the identity table --, the SDWA byte chains of
@@ -205,7 +178,7 @@ def test_requant_unit_is_within_the_encoder_budget(tmp_path):
     store_row_pair / store_rows_edge), no scratch, no spills, no DPP, no traps, no static LDS (the table sits at LDS offset 0),
     and the VGPRs within the 96 of the five waves per SIMD the launch bounds declare."""
     import check_isa
-    path = _isa(tmp_path)
+    path = CL.isa("requant", tmp_path)
     r = check_isa.check(path)
     assert r["kernels"] == 4, r
     assert r["partial_writes"] > 400, r
@@ -215,11 +188,7 @@ def test_requant_unit_is_within_the_encoder_budget(tmp_path):
     assert len(set(re.findall(r"\b(_Z\w*k_requant\w*):", text))) == 4
     assert "k_enc_tiles" not in text and "k_enc_pitched" not in text and "k_dec_tiles" not in text
     assert re.search(r"buffer_store_dwordx4 .* nt", text)
-    res = {}
-    for m in re.finditer(r"\.group_segment_fixed_size:\s*(\d+).*?\.name:\s*(\S+).*?\.private_segment_fixed_size:\s*(\d+).*?\.vgpr_count:\s*(\d+)",
-                         text, flags=re.S):
-        if "k_requant" in m.group(2):
-            res[m.group(2)] = (int(m.group(4)), int(m.group(1)), int(m.group(3)))
+    res = CL.resources(text, "k_requant")
     assert len(res) == 4, res
     seen = set()
     for k, (vgprs, lds, scratch) in res.items():
@@ -230,14 +199,8 @@ def test_requant_unit_is_within_the_encoder_budget(tmp_path):
         # 512 VGPRs per SIMD lane, allocated in eights: five waves -> at most 96
         assert vgprs <= 96, (k, vgprs)
     assert seen == {(i, s) for i in (0, 1) for s in (0, 2)}
-    src = open(os.path.join(REQUANT_DIR, "hgi_fused_requant.hip")).read()
+    src = CL.unit_source("requant", "hgi_fused_enc.hip")      # ... the uniform encoder's dynamic LDS, nothing added
     assert "amdgpu_waves_per_eu(HGI_ENC_WAVES_PER_EU)" in src
-    assert '#include "../csrc/hgi_fused_enc.hip"' in src and '#include "../csrc/hgi_fused_pitched.h"' in src
-    assert "#define HGI_FUSED_NO_LAUNCHERS 1" in src
-    entry = open(os.path.join(CL.COMPANION_DIR, "hgi_entry.h")).read()      # the launcher's check, shared by the four units
-    assert "static_lds_is_empty(reinterpret_cast" in src and '#include "../companion/hgi_entry.h"' in src
-    assert "hipFuncGetAttributes" in entry and "sharedSizeBytes == 0" in entry
-    assert "(size_t)buf_bytes(nh) + ((rbuf_bytes(nh) + 15) & ~15) + 256" in src      # the uniform encoder's dynamic LDS, nothing added
 
 
 # -------------------------------------------------------------------------------------------------------- host plan
@@ -245,11 +208,7 @@ def test_plan_and_intervals_under_asan_ubsan(tmp_path):
     """tests/cpp/test_requant_plan.cpp, a stand-alone program: random shapes, pitches, alignments and batches; every block
     walked through the map, every 32-bit offset of both sides bounded, the `fast` rule, the tail rule and the interval test
     against plain 64-bit arithmetic and brute force."""
-    exe = str(tmp_path / "test_requant_plan")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", os.path.join(ROOT, "tests", "cpp", "test_requant_plan.cpp"), "-o", exe])
-    p = subprocess.run([exe, "1500", "0x48474939"], capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0 and "1500 cases, 0 failures" in p.stdout, p.stdout[-3000:] + p.stderr[-3000:]
+    CL.run_plan_program("requant", tmp_path, flags=("-Werror",))
 
 
 # ------------------------------------------------------------------------------ oracle facts the design rests on
@@ -479,6 +438,4 @@ def test_python_mirror_refuses_bad_views_before_any_device_call(Q):
 
 
 def test_build_entry_builds_the_companion_library():
-    src = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert '"rustyhgi_amd", "requant"' in src
-    assert "rustyhgi_amd/requant/_obj*/" in open(os.path.join(ROOT, ".gitignore")).read()
+    CL.check_build_entry("requant")

@@ -28,16 +28,11 @@ ARGS = ["hip_stream", "d_img", "img_pitch", "elem_size", "elem_kind", "scale", "
 
 @pytest.fixture(scope="module")
 def T():
-    """The binding, with the library built first if it is missing."""
-    from rustyhgi_amd import _ffi_typed
-    if not os.path.exists(_ffi_typed.LIB_PATH):
-        subprocess.check_call(["make", "-s", "-C", TYPED_DIR, "-j4", "all"])
-    _ffi_typed.lib()
-    return _ffi_typed
+    return CL.binding("typed")
 
 
 def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hgi_typed.h")).read(), flags=re.S)
+    return CL.header("typed")
 
 
 def test_library_exports_exactly_the_three_entry_points(T):
@@ -94,12 +89,6 @@ def test_ctypes_table_matches_the_header(T):
     # the header takes hgi_status / hgi_interp from hgi.h and declares no type of its own
     assert '#include "hgi.h"' in open(os.path.join(ROOT, "include", "hgi_typed.h")).read()
     assert not re.search(r"\b(typedef|struct|enum)\b", _header())
-
-
-def _page_aligned(n):
-    raw = np.zeros(n + 8192, np.uint8)
-    off = (-raw.ctypes.data) % 4096
-    return raw, raw.ctypes.data + off
 
 
 def test_c_abi_refuses_bad_arguments_without_a_device(T):
@@ -163,7 +152,7 @@ def test_c_abi_refuses_bad_arguments_without_a_device(T):
     assert call(interp=7, **far) == U and b"interpolator" in err()
     assert call(interp=-1, **far) == U
     # 2-byte elements of an odd width whose span ends a page: the two tail bytes leave it (synthetic addresses)
-    raw, page = _page_aligned(3 * 4096)
+    raw, page = CL.page_aligned(3 * 4096)
     w, h, ip = 31, 8, 72
     span = (h - 1) * ip + 2 * w
     assert call(img=page + 4096 - span, w=w) == U and b"tail" in err() and b"4-KiB" in err()
@@ -186,24 +175,7 @@ def test_c_abi_refuses_bad_arguments_without_a_device(T):
 
 def test_entry_point_decides_every_rule_before_the_first_hip_call():
     """hgi_typed.hip: in the entry point no HIP call stands before the launch, and the launch stands behind the last refusal."""
-    src = open(os.path.join(TYPED_DIR, "hgi_typed.hip")).read()
-    body = src[src.index("hgi_status hgi_typed_encode_dev("):src.index("const char *hgi_typed_last_error")]
-    first_hip = min(m.start() for m in re.finditer(r"\bhip[A-Z]\w*\s*\(|launch_encode_typed\s*\(", body))
-    assert body[first_hip:].startswith("launch_encode_typed(")
-    assert "return fail(HGI_EINVAL" not in body[first_hip:] and "return fail(HGI_EUNSUPPORTED" not in body[first_hip:]
-    assert body.index("return HGI_OK;") < body.index("return fail(")      # the empty call is decided first
-    # every HGI_EINVAL rule stands before the first HGI_EUNSUPPORTED one
-    assert max(m.start() for m in re.finditer(r"fail\(HGI_EINVAL", body)) < min(m.start() for m in re.finditer(r"fail\(HGI_EUNSUPPORTED", body))
-
-
-def _isa(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path / "hgi_fused_typed_enc.s")
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S",
-                           os.path.join(TYPED_DIR, "hgi_fused_typed_enc.hip"), "-o", out], stderr=subprocess.DEVNULL)
-    return out
+    CL.check_rule_order("typed", "hgi_typed_encode_dev", "launch_encode_typed")
 
 
 @pytest.mark.timeout(900)
@@ -214,7 +186,7 @@ def test_typed_unit_is_within_its_budgets(tmp_path):
     encoder's -- and the conversion as the header words it: float32 denormals kept, a multiply and an add
     and never a fused one, round to nearest even, one saturating conversion."""
     import check_isa
-    path = _isa(tmp_path)
+    path = CL.isa("typed", tmp_path)
     r = check_isa.check(path)
     assert r["kernels"] == 16, r
     assert r["partial_writes"] > 400, r
@@ -226,11 +198,7 @@ def test_typed_unit_is_within_its_budgets(tmp_path):
     assert not re.search(r"\bv_(pk_)?(fma|fmac|mac|mad)_(f32|legacy_f32)", text), "the conversion's two operations must stay two"
     assert "v_mul_f32" in text and "v_add_f32" in text and "v_rndne_f32" in text and "v_cvt_u32_f32" in text and "v_cvt_f32_f16" in text
     assert re.search(r"buffer_store_dwordx4 .* nt", text)
-    res = {}
-    for m in re.finditer(r"\.group_segment_fixed_size:\s*(\d+).*?\.name:\s*(\S+).*?\.private_segment_fixed_size:\s*(\d+).*?\.vgpr_count:\s*(\d+)",
-                         text, flags=re.S):
-        if "k_enc_typed" in m.group(2):
-            res[m.group(2)] = (int(m.group(4)), int(m.group(1)), int(m.group(3)))
+    res = CL.resources(text, "k_enc_typed")
     assert len(res) == 16, res
     assert len(re.findall(r"\.amdhsa_float_denorm_mode_32 3\b", text)) == 16 and not re.search(r"\.amdhsa_float_denorm_mode_32 [012]\b", text)
     # 512 VGPRs per SIMD lane, allocated in eights: waves w -> at most (512 / w) rounded down to a multiple of 8
@@ -244,26 +212,16 @@ def test_typed_unit_is_within_its_budgets(tmp_path):
         assert lds == 0 and scratch == 0, (k, lds, scratch)
         assert vgprs <= budget[(seeded, e)], (k, vgprs)
     assert seen == {(i, d, s, e) for i in (0, 1) for d in (0, 1) for s in (0, 2) for e in (2, 4)}
-    src = open(os.path.join(TYPED_DIR, "hgi_fused_typed_enc.hip")).read()
+    src = CL.unit_source("typed", "hgi_fused_enc.hip")      # ... the uniform encoder's dynamic LDS, nothing added
     assert "constexpr int kTypedWavesPerEu = HGI_ENC_WAVES_PER_EU;" in src
     assert "amdgpu_waves_per_eu(kTypedWavesPerEu)" in src
-    assert '#include "../csrc/hgi_fused_enc.hip"' in src and '#include "../csrc/hgi_fused_pitched.h"' in src
-    assert "#define HGI_FUSED_NO_LAUNCHERS 1" in src
-    entry = open(os.path.join(CL.COMPANION_DIR, "hgi_entry.h")).read()      # the launcher's check, shared by the four units
-    assert "static_lds_is_empty(reinterpret_cast" in src and '#include "../companion/hgi_entry.h"' in src
-    assert "hipFuncGetAttributes" in entry and "sharedSizeBytes == 0" in entry
-    assert "(size_t)buf_bytes(nh) + ((rbuf_bytes(nh) + 15) & ~15) + 256" in src      # the uniform encoder's dynamic LDS, nothing added
 
 
 def test_plan_and_intervals_under_asan_ubsan(tmp_path):
     """tests/cpp/test_typed_plan.cpp, a stand-alone program: random shapes, pitches, strides, addresses, batches and element
     sizes; every block walked through the map, every 32-bit offset of both sides bounded against the records, the fits, page
     and interval rules against brute force."""
-    exe = str(tmp_path / "test_typed_plan")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", os.path.join(ROOT, "tests", "cpp", "test_typed_plan.cpp"), "-o", exe])
-    p = subprocess.run([exe, "1500", "0x48474939"], capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0 and "1500 cases, 0 failures" in p.stdout, p.stdout[-3000:] + p.stderr[-3000:]
+    CL.run_plan_program("typed", tmp_path)
 
 
 def _torch_quantize(x, scale, bias):
@@ -369,7 +327,4 @@ def test_python_mirror_refuses_bad_arguments_before_any_device_call(T):
 
 
 def test_build_entry_builds_the_companion_library():
-    src = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert '"rustyhgi_amd", "typed"' in src
-    assert src.index('"rustyhgi_amd", "map"') < src.index('"rustyhgi_amd", "typed"')
-    assert "rustyhgi_amd/typed/_obj*/" in open(os.path.join(ROOT, ".gitignore")).read()
+    CL.check_build_entry("typed", after="map")
