@@ -6,15 +6,19 @@ plus rustyhgi_amd.entropy (device-side byte histogram of the grid)
 buffers placed for MI355X's HBM regions, include/hgi.h hgi_planes_alloc) and rustyhgi_amd.mapping (the 256-entry tables of
 Decoder.decode_mapped, include/hgi_map.h, and the constants of Encoder.encode_typed, include/hgi_typed.h).
 Encoder.requantize re-codes stored grids with another table in one launch (libhgi_requant.so, include/hgi_requant.h).
+rustyhgi_amd.views (ViewPlan, aligned_arena) plans view lists -- frames with a pitch of their own each -- for Encoder.encode_views /
+Decoder.decode_views: one launch per list (libhgi_views.so, include/hgi_views.h).
 All computation happens in libhgi_hip.so (hand-written HIP kernels); see include/hgi.h.
 """
-from . import entropy, interpolator, mapping, quantizator
+from . import entropy, interpolator, mapping, quantizator, views
 from ._ffi import Context, HgiError, default_context
 from .archive import Archive, Metadata
 from .codec import Decoder, Encoder
 from .grid import Grid
 from .mapping import affine_inverse, affine_table
 from .planes import Planes
+from .views import ViewPlan, aligned_arena
 
 __all__ = ["Encoder", "Decoder", "Grid", "Archive", "Metadata", "Context", "HgiError", "default_context", "interpolator",
-           "quantizator", "entropy", "Planes", "mapping", "affine_table", "affine_inverse"]
+           "quantizator", "entropy", "Planes", "mapping", "affine_table", "affine_inverse", "views", "ViewPlan",
+           "aligned_arena"]

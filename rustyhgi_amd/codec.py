@@ -342,6 +342,33 @@ def _map_table(table, grids, what):
     return table.dtype, esize, (table.ctypes.data, table.ctypes.data + 256 * esize)
 
 
+def _views_launch(plan, ctx, fused, each):
+    """One view-list call on plan.device: `fused(stream, d_plan, info)` -> status of the one launch; `each(ctx, view layout)` ->
+    status of one pitched call, composed per view when the plan or the launch is not served (HGI_EUNSUPPORTED).  Returns the
+    plan's destination views."""
+    import torch
+    from . import _ffi_views
+    if len(plan) == 0 or plan.device is None:
+        return list(plan.dsts)
+    dev = plan.device.index if plan.device.index is not None else torch.cuda.current_device()
+    if ctx is not None and ctx.device != dev:      # both routes judge the context alike (_bind_ctx)
+        raise ValueError("the views live on cuda:%d but the context was created for cuda:%d" % (dev, ctx.device))
+    st = _ffi.EUNSUPPORTED
+    if plan.fused:
+        if plan.blob is None:      # only empty views
+            return list(plan.dsts)
+        with torch.cuda.device(dev):
+            st = fused(_ffi._vp(torch.cuda.current_stream(dev).cuda_stream or 0), plan.blob.data_ptr(), ctypes.addressof(plan.info))
+    if st == _ffi.EUNSUPPORTED:      # not served by the one launch: the same bytes from one pitched call per view
+        bound = _bind_ctx(plan.srcs[0], ctx)
+        for lay in plan.layouts:
+            if lay[2] and lay[3]:
+                _ffi.check(each(bound, lay))
+        return list(plan.dsts)
+    _ffi_views.check(st)
+    return list(plan.dsts)
+
+
 def _np_image(a):
     a = np.ascontiguousarray(a, dtype=np.uint8)
     if a.ndim != 2:
@@ -591,6 +618,21 @@ class Encoder:
         _ffi_typed.check(st)
         return out
 
+    def encode_views(self, plan):
+        """Encode a VIEW LIST: `plan` is a `rustyhgi_amd.views.ViewPlan` of (image view, grid view) pairs -- every pair with a
+        shape and two row pitches of its own.  Each destination view, read through its pitch, is bit for bit `encode_view` of
+        its source view alone; only the W-byte rows of the destinations are written.  ONE hgi_views_encode_dev launch
+        (libhgi_views.so), asynchronous on the current stream and capturable into a graph; the plan may be launched any number
+        of times.  What that launch does not serve (HGI_EUNSUPPORTED: 0 or more than 8 levels, an entry beyond the 32-bit
+        buffer path or with its last source bytes at the end of a 4-KiB page) is composed from one hgi_encode_u8_pitched_dev
+        call per view: the same bytes, not fused.  Returns the destination views."""
+        from . import _ffi_views
+        lut, levels, interp = self._lut.ctypes.data, self.scale_level, self._interp
+        return _views_launch(
+            plan, self._ctx,
+            lambda stream, blob, info: _ffi_views.lib().hgi_views_encode_dev(stream, blob, info, levels, interp, lut),
+            lambda ctx, v: _ffi.lib().hgi_encode_u8_pitched_dev(ctx.handle, v[0], v[4], v[2], v[3], levels, interp, lut, v[1], v[5], 1, 0, 0))
+
     def encode_list(self, images, out=None):
         """A list of (h_i, w_i) uint8 frames of any shapes -> the list of their residual planes.  CUDA tensors (one device,
         contiguous): ONE hgi_encode_u8_list_dev call, asynchronous on the current stream, the outputs (h_i, w_i) views into one
@@ -798,6 +840,17 @@ class Decoder:
         ins, ws, hs, ptrs = _list_arrays(frames, outs)
         _ffi.check(_ffi.lib().hgi_decode_u8_list_dev(ctx.handle, ins, ws, hs, int(levels), self._interp, ptrs, len(frames)))
         return outs
+
+    def decode_views(self, plan, levels):
+        """Decode a VIEW LIST: `plan` is a `rustyhgi_amd.views.ViewPlan` of (grid view, image view) pairs, all coded with
+        `levels` (see Encoder.encode_views).  ONE hgi_views_decode_dev launch; what it does not serve is composed from one
+        hgi_decode_u8_pitched_dev call per view.  Returns the destination views."""
+        from . import _ffi_views
+        levels, interp = int(levels), self._interp
+        return _views_launch(
+            plan, self._ctx,
+            lambda stream, blob, info: _ffi_views.lib().hgi_views_decode_dev(stream, blob, info, levels, interp),
+            lambda ctx, v: _ffi.lib().hgi_decode_u8_pitched_dev(ctx.handle, v[0], v[4], v[2], v[3], levels, interp, v[1], v[5], 1, 0, 0))
 
     def decode_mapped(self, grids, levels, table, out=None):
         """Decode a view of grids straight into frames of the `table`'s dtype: `out[..., y, x] = table[decoded[..., y, x]]`,
