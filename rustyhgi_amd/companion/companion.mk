@@ -18,7 +18,7 @@ COMPANION := ../companion
 
 all: $(OUT)
 
-$(OBJ)/%.o: %.hip hgi_$(NAME)_plan.h hgi_$(NAME)_kernels.h $(COMPANION)/hgi_sides.h $(COMPANION)/hgi_entry.h $(COMPANION)/hgi_tile.h $(CSRC)/hgi_kernels.h $(CSRC)/hgi_dev.h $(CSRC)/hgi_fused_impl.h $(CSRC)/$(FUSED) $(CSRC)/hgi_fastdiv.h $(CSRC)/hgi_tilewalk.h $(CSRC)/hgi_pitched.h $(CSRC)/hgi_fused_pitched.h $(CSRC)/hgi_knobs.h ../../include/hgi.h ../../include/hgi_$(NAME).h $(ALSO)
+$(OBJ)/%.o: %.hip hgi_$(NAME)_plan.h hgi_$(NAME)_kernels.h $(COMPANION)/hgi_sides.h $(COMPANION)/hgi_entry.h $(COMPANION)/hgi_tile.h $(CSRC)/hgi_kernels.h $(CSRC)/hgi_dev.h $(CSRC)/hgi_fused_impl.h $(CSRC)/$(FUSED) $(CSRC)/hgi_fastdiv.h $(CSRC)/hgi_tilewalk.h $(CSRC)/hgi_pitched.h $(CSRC)/hgi_fused_pitched.h $(CSRC)/hgi_knobs.h $(CSRC)/hgi_launch_policy.h $(CSRC)/hgi_launch.h $(CSRC)/hgi_dec_chain.h ../../include/hgi.h ../../include/hgi_$(NAME).h $(ALSO)
 	@mkdir -p $(OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) $(EXTRA) -c $< -o $@
 

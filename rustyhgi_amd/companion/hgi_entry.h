@@ -1,5 +1,5 @@
-// What the HIP units of the companion libraries share: the error text of the calling thread and the launchers' check that a
-// kernel has no static LDS.  Each library gets a copy of its own (nothing here is exported, nothing is linked in common).
+// What the HIP units of the companion libraries share: the error text of the calling thread.  Each library gets a copy of its
+// own (nothing here is exported, nothing is linked in common).
 // Stateless like its users: no environment, no allocation, no context.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -20,16 +20,6 @@ __attribute__((format(printf, 2, 3))) inline hgi_status fail(hgi_status st, cons
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
     return st;
-}
-
-// The kernels address the quantizer's table from LDS offset 0 (lut_at()): a launcher checks once per instantiation that the
-// compiler placed no static LDS in front of it.
-inline hipError_t static_lds_is_empty(const void *kernel)
-{
-    hipFuncAttributes fa;
-    const hipError_t e = hipFuncGetAttributes(&fa, kernel);
-    if (e != hipSuccess) return e;
-    return fa.sharedSizeBytes == 0 ? hipSuccess : hipErrorInvalidDeviceFunction;
 }
 
 }  // namespace hgi

@@ -109,21 +109,6 @@ static_assert(TH != 64 || 18 * (buf_bytes(4) + rbuf_bytes(4) + 256) <= 160 * 102
 #ifndef HGI_DEC_CONE_FIRST
 #define HGI_DEC_CONE_FIRST 0     // the decoder's cone load in front of the tile's staging loads (1) or behind them (0)
 #endif
-#ifndef HGI_DEC_SHALLOW_WAVES
-#define HGI_DEC_SHALLOW_WAVES 20  // resident tiles per CU asked for on decodes 1-8 rounds deep (launch_decode_fused)
-#endif
-#ifndef HGI_DEC_DEEP_WAVES
-#define HGI_DEC_DEEP_WAVES 16     // ... and on deeper ones (launches that rebuild levels in the kernel or start from seed planes)
-#endif
-#ifndef HGI_DEC_STREAM_WAVES
-#define HGI_DEC_STREAM_WAVES 10   // resident tiles per CU of a plain decode (the tile holds the pyramid) of 8 192 tiles and more, rows up
-#endif                            // to 4 096 pixels and up to four levels ...
-#ifndef HGI_DEC_STREAM_WAVES_WIDE
-#define HGI_DEC_STREAM_WAVES_WIDE 12   // ... and on wider rows or five levels
-#endif
-#ifndef HGI_DEC_STREAM_WAVES_L1
-#define HGI_DEC_STREAM_WAVES_L1 8      // ... and at ONE level (the finest pass alone: a tile's lifetime is shortest there)
-#endif
 #ifndef HGI_XCD_MODE
 #define HGI_XCD_MODE -1     // the XCD dealing policy (block_role): 0 contiguous eighths, 1 whole bands round-robin, -1 by size (xcd_mode())
 #endif
@@ -983,6 +968,33 @@ __device__ __forceinline__ void dec_level2_fast(u8 *buf, int rows = TH, int cols
     }
 }
 
+// The arithmetic of the finest pass on one task of a lane, for dec_fine_fast and for the decoders that bring a store of their own
+// (region decode, the companions' mapped and requantizing ones): E, F the lattice rows above and below as loaded, e16 / f16 their
+// ninth corners, O the residuals of row y + 1.  Out come row y (E with its odd columns decoded) and row y + 1.  The loads and the
+// choice of the ninth corner stay with the caller: moved in here too, the scheduler orders them differently in the Crossed kernels.
+template <int INTERP>
+__device__ __forceinline__ void dec_fine_rows(v4u E, v4u F, u32 e16, u32 f16, v4u O, v4u &r0v, v4u &r1v)
+{
+    uint2 c, fl;
+    c.x = __builtin_amdgcn_perm(E.y, E.x, 0x06040200u);
+    c.y = __builtin_amdgcn_perm(E.w, E.z, 0x06040200u);
+    fl.x = __builtin_amdgcn_perm(F.y, F.x, 0x06040200u);
+    fl.y = __builtin_amdgcn_perm(F.w, F.z, 0x06040200u);
+    u32 P0, P1;
+    pred8<INTERP>(c, e16, fl, f16, P0, P1);
+    u32 e0 = E.x, e1 = E.y, e2 = E.z, e3 = E.w, o0 = O.x, o1 = O.y, o2 = O.z, o3 = O.w;
+    // row y: odd columns;  cell j of the lane = byte j of P0 (j < 4) or byte j-4 of P1
+    HGI_ADDB(e0, 1, P0, 0); HGI_ADDB(e0, 3, P0, 1); HGI_ADDB(e1, 1, P0, 2); HGI_ADDB(e1, 3, P0, 3);
+    HGI_ADDB(e2, 1, P1, 0); HGI_ADDB(e2, 3, P1, 1); HGI_ADDB(e3, 1, P1, 2); HGI_ADDB(e3, 3, P1, 3);
+    // row y+1: every column
+    HGI_ADDB(o0, 0, P0, 0); HGI_ADDB(o0, 1, P0, 0); HGI_ADDB(o0, 2, P0, 1); HGI_ADDB(o0, 3, P0, 1);
+    HGI_ADDB(o1, 0, P0, 2); HGI_ADDB(o1, 1, P0, 2); HGI_ADDB(o1, 2, P0, 3); HGI_ADDB(o1, 3, P0, 3);
+    HGI_ADDB(o2, 0, P1, 0); HGI_ADDB(o2, 1, P1, 0); HGI_ADDB(o2, 2, P1, 1); HGI_ADDB(o2, 3, P1, 1);
+    HGI_ADDB(o3, 0, P1, 2); HGI_ADDB(o3, 1, P1, 2); HGI_ADDB(o3, 2, P1, 3); HGI_ADDB(o3, 3, P1, 3);
+    r0v = v4u{e0, e1, e2, e3};
+    r1v = v4u{o0, o1, o2, o3};
+}
+
 // finest level: 16 px x 2 rows per lane; even rows from LDS, odd rows from the registers they were loaded
 // into, packed VALU, 16-B buffer stores
 // EDGE: only the `rows` x `cols` part of the tile that lies inside the image is stored.
@@ -1005,23 +1017,8 @@ __device__ __forceinline__ void dec_fine_fast(const u8 *buf, const Buf &b, const
         const u32 he = h0[0], hf = h0[1];
         e16 = last ? he : e16;
         f16 = last ? hf : f16;
-        uint2 c, fl;
-        c.x = __builtin_amdgcn_perm(E.y, E.x, 0x06040200u);
-        c.y = __builtin_amdgcn_perm(E.w, E.z, 0x06040200u);
-        fl.x = __builtin_amdgcn_perm(F.y, F.x, 0x06040200u);
-        fl.y = __builtin_amdgcn_perm(F.w, F.z, 0x06040200u);
-        u32 P0, P1;
-        pred8<INTERP>(c, e16, fl, f16, P0, P1);
-        u32 e0 = E.x, e1 = E.y, e2 = E.z, e3 = E.w, o0 = O.x, o1 = O.y, o2 = O.z, o3 = O.w;
-        // row y: odd columns;  cell j of the lane = byte j of P0 (j < 4) or byte j-4 of P1
-        HGI_ADDB(e0, 1, P0, 0); HGI_ADDB(e0, 3, P0, 1); HGI_ADDB(e1, 1, P0, 2); HGI_ADDB(e1, 3, P0, 3);
-        HGI_ADDB(e2, 1, P1, 0); HGI_ADDB(e2, 3, P1, 1); HGI_ADDB(e3, 1, P1, 2); HGI_ADDB(e3, 3, P1, 3);
-        // row y+1: every column
-        HGI_ADDB(o0, 0, P0, 0); HGI_ADDB(o0, 1, P0, 0); HGI_ADDB(o0, 2, P0, 1); HGI_ADDB(o0, 3, P0, 1);
-        HGI_ADDB(o1, 0, P0, 2); HGI_ADDB(o1, 1, P0, 2); HGI_ADDB(o1, 2, P0, 3); HGI_ADDB(o1, 3, P0, 3);
-        HGI_ADDB(o2, 0, P1, 0); HGI_ADDB(o2, 1, P1, 0); HGI_ADDB(o2, 2, P1, 1); HGI_ADDB(o2, 3, P1, 1);
-        HGI_ADDB(o3, 0, P1, 2); HGI_ADDB(o3, 1, P1, 2); HGI_ADDB(o3, 2, P1, 3); HGI_ADDB(o3, 3, P1, 3);
-        v4u r0v = {e0, e1, e2, e3}, r1v = {o0, o1, o2, o3};
+        v4u r0v, r1v;
+        dec_fine_rows<INTERP>(E, F, e16, f16, O, r0v, r1v);
         if (EDGE == 2) {
             const int y = 2 * (rp0 + it * (NL / CH));
             store_rows_edge(r0v, r1v, b.rd, voff, __builtin_amdgcn_readfirstlane(b.W), cols - 16 * (lane & (CH - 1)), y < rows, y + 1 < rows);
@@ -1870,16 +1867,6 @@ inline u32 band_rows(const Frames &f, bool encode)
 
 // (finish_grid -- everything the kernels would otherwise derive per block from the launch's constants: hgi_tilewalk.h)
 
-// Dynamic LDS of a launch padded so that at most `waves` blocks fit a CU (160 KiB of LDS): a launch only a few rounds of
-// resident tiles deep pays a tile LIFETIME for filling and draining the chip, and the lifetime is resident tiles / rate
-// (Little) -- fewer resident tiles at the same rate shorten it.  (Knobs build: HGI_DEC_WAVES / HGI_ENC_WAVES, tools/waves_sweep.sh.)
-inline size_t lds_for_waves(size_t lds, int waves)
-{
-    if (waves <= 0) return lds;
-    const size_t cap = ((size_t)160 * 1024 / (size_t)waves) & ~(size_t)255;
-    return cap > lds ? cap : lds;
-}
-
 // How the band-ordered tile list is dealt to the eight XCDs (block_role).  Whole bands round-robin -- the chip works on eight
 // CONSECUTIVE bands -- is what a launch up to a few GiB wants: contiguous eighths put the XCDs' eight working points a
 // power-of-two distance of 32 ... 256 MiB apart, and those streams beat against each other in the memory system (16384^2:
@@ -1902,6 +1889,12 @@ inline u32 xcd_mode(const TileGrid &g, bool encode)
 }
 
 }  // namespace
+
+}  // namespace hgi
+
+#include "hgi_launch.h"      // behind the tile procedure: it names buf_bytes, rbuf_bytes and NL
+
+namespace hgi {
 
 // The host launchers of the tile builds.  A unit that includes this file for the tile procedure alone and brings a launcher of
 // its own (hgi_fused_region.hip) defines HGI_FUSED_NO_LAUNCHERS: these would be defined twice at link time.
@@ -1927,69 +1920,24 @@ hipError_t HGI_TILED(launch_decode_fused)(const uint8_t *grid, uint8_t *img, con
     const bool cone = seeds && seeds->up != 0;
     if (cone && (k != 4 || sd.up > (u32)kConeMaxUp)) return hipErrorInvalidValue;
     if (seeds && !cone && !seeds->rec) return hipErrorInvalidValue;
-    const dim3 b(NL);
     const int nh = k >= 2 ? (int)k : 1;
-    // How many tiles a CU holds at one time (the dynamic LDS is padded to that: lds_for_waves).  Its LDS would allow 32.
-    //  * Fewer than 8 192 tiles: all it can get -- the launch ends when its slowest wave does.
-    //  * A PLAIN decode (the tile holds the pyramid: no seeds) of 8 192 tiles and more: TEN on rows up to 4 096 pixels and up to
-    //    four levels, twelve otherwise.  Round 4, in-process A/B of builds on the same placed planes (tools/ab.py,
-    //    profiles/r04_ab_dec_waves.txt): 64 x 4096^2 level 4 against the 16 of the round's first builds: 9 tiles -1.9 %, 10 -5.2 %,
-    //    11 -3.1 %, 12 -0.8 %; 256 x -6.3 %, 512 x -5.5 % (2.789 -> 2.636 ms = 0.815 of 8 TB/s), 40 / 24 / 16 x -4.3 / -4.1 / -3.4 %,
-    //    8 x -0.8 %; levels 1 / 2 -1.4 / -2.1 %; 300 x 1920 x 1080 -2.3 %.  On 8192- and 16384-wide rows and at five levels twelve
-    //    is the better number (-2.8 / -2.3 ... -3.6 / -2.0 % against -2.4 / -0.6 ... -2.3 / -0.2 % at ten).  The likely reason:
-    //    with ten tiles per CU the 320 tiles an XCD has in flight read 2.7 MB at a time, which -- halo lines included -- stays in
-    //    its 4 MB L2; at 16 and more it does not (round 1 counted 1.06 x the algorithmic bytes fetched at 32); below ten the
-    //    latency is no longer covered.  At ONE level (the finest pass alone, P_fine) eight: 64 x 4096^2 0.3360 -> 0.3277 ms, 512 x
-    //    2.768 -> 2.692 (profiles/r04_ab_pfine.txt).
-    //  * A decode that rebuilds levels above its tiles (the cone) or starts from seed planes: 20 on launches one to eight
-    //    rounds of resident tiles deep (8 192 ... 65 536 tiles: a lone 16384^2 frame at level 8 has 32 768; the tile lifetime --
-    //    what filling and draining the chip costs -- is shorter at the same rate: 101.3 us at 32, 99.1 at 20, 98.5 at 16, 109.8
-    //    at 12, profiles/r03_waves_sweep.txt), 16 on deeper ones; these lose with ten or twelve (+3 ... +10 %: the cone's far
-    //    loads and its walk want the occupancy).  (The encoder needs all 20 it can get: 98 us, 106 at 16.)
-    const int dec_waves_forced = HGI_KNOB(HGI_DEC_WAVES, -1);
-    const u64 tiles = (u64)g.nfast + g.nedge;
-    int dec_waves = 0;
-    if (resident_tiles >= 0)
-        dec_waves = resident_tiles;      // the caller's choice (the placement probe, hgi_planes.hip: it has to keep measuring the
-                                         // same thing whatever the policy or a knob says)
-    else if (dec_waves_forced >= 0)
-        dec_waves = dec_waves_forced;
-    else if (tiles < 8192)
-        dec_waves = 0;
-    else if (!seeds)
-        dec_waves = f.width > 4096 || k > 4 ? HGI_DEC_STREAM_WAVES_WIDE : k == 1 ? HGI_DEC_STREAM_WAVES_L1 : HGI_DEC_STREAM_WAVES;
-    else
-        dec_waves = tiles >= 65536 ? HGI_DEC_DEEP_WAVES : HGI_DEC_SHALLOW_WAVES;
-    const size_t lds = lds_for_waves((size_t)buf_bytes(nh), dec_waves);
+    // resident tiles per CU: the caller's choice (the placement probe, hgi_planes.hip: it has to keep measuring the same thing
+    // whatever the policy or a knob says), or the policy's
+    const int waves = resident_tiles >= 0 ? resident_tiles : dec_resident_tiles((u64)g.nfast + g.nedge, f.width, k, seeds != nullptr);
+    const size_t lds = lds_for_waves((size_t)buf_bytes(nh), waves);
     const dim3 blocks(((g.nedge + 7u) & ~7u) + g.nfast);
-#define HGI_DEC(I, SE) hipLaunchKernelGGL((k_dec_tiles<I, SE, TH>), blocks, b, lds, s, grid, img, f, k, sd, g, r.aligned)
-    // (seed PLANES without a cone -- SEEDED == 1 -- exist for 64-row tiles only: six fused levels, hgi_capi.hip host_banded)
-#define HGI_DEC_I(I)                                                     \
-    do {                                                                 \
-        if (!seeds) HGI_DEC(I, 0);                                       \
-        else if (cone) HGI_DEC(I, 2);                                    \
-        else if constexpr (TH == 64) HGI_DEC(I, 1);                      \
-        else return hipErrorInvalidValue;                                \
-    } while (0)
-    if (interp == kInterpCrossed) HGI_DEC_I(kInterpCrossed); else HGI_DEC_I(kInterpLeftTop);
-#undef HGI_DEC_I
-#undef HGI_DEC
-    return hipGetLastError();
+    return with_choices(
+        [&](auto I, auto SE) {
+            // (seed PLANES without a cone -- SEEDED == 1 -- exist for 64-row tiles only: six fused levels, hgi_capi.hip host_banded)
+            if constexpr (SE == 1 && TH != 64) return hipErrorInvalidValue;
+            else return launch_tile_kernel<k_dec_tiles<I, SE, TH>>(blocks, lds, s, grid, img, f, k, sd, g, r.aligned);
+        },
+        interp_choice(interp), OneOf<0, 2, 1>{!seeds ? 0 : cone ? 2 : 1});
 }
 
 #endif  // HGI_FUSED_DECODE
 
 #ifdef HGI_FUSED_ENCODE
-namespace {
-hipError_t static_lds_is_empty(const void *kernel)
-{
-    hipFuncAttributes a;
-    const hipError_t e = hipFuncGetAttributes(&a, kernel);
-    if (e != hipSuccess) return e;
-    return a.sharedSizeBytes == 0 ? hipSuccess : hipErrorInvalidDeviceFunction;
-}
-}  // namespace
-
 hipError_t HGI_TILED(launch_encode_fused)(const uint8_t *img, uint8_t *grid, const Frames &f, uint32_t k, int interp,
                                           const Lut256 &lut, bool ident, const Seeds *seeds, hipStream_t s, uint32_t row_limit)
 {
@@ -2005,36 +1953,16 @@ hipError_t HGI_TILED(launch_encode_fused)(const uint8_t *img, uint8_t *grid, con
     const bool cone = seeds && seeds->up != 0;
     if (cone && (k != 4 || sd.up > (u32)kConeMaxUp)) return hipErrorInvalidValue;
     if (seeds && (!seeds->rec != !seeds->q || (!cone && !seeds->rec))) return hipErrorInvalidValue;
-    const dim3 b(NL);
     const int nh = k >= 2 ? (int)k : 1;
-    const int enc_waves = HGI_KNOB(HGI_ENC_WAVES, 0);
-    const size_t lds = lds_for_waves((size_t)buf_bytes(nh) + ((rbuf_bytes(nh) + 15) & ~15) + 256, enc_waves);
+    const size_t lds = lds_for_waves(enc_lds_bytes(nh), HGI_KNOB(HGI_ENC_WAVES, 0));
     const dim3 blocks(((g.nedge + 7u) & ~7u) + g.nfast);
-    // lut_at() addresses the table from LDS offset 0: only valid while the kernel has no static LDS in front of its
-    // dynamic segment.  Checked once per instantiation on the host; a build that breaks it fails here, not on the device.
-#define HGI_ENC(I, ID, SE)                                                                                        \
-    do {                                                                                                          \
-        static const hipError_t lds0 = static_lds_is_empty(reinterpret_cast<const void *>(&k_enc_tiles<I, ID, SE, TH>)); \
-        if (lds0 != hipSuccess) return lds0;                                                                      \
-        hipLaunchKernelGGL((k_enc_tiles<I, ID, SE, TH>), blocks, b, lds, s, img, grid, f, k, lut, sd, g, r.aligned); \
-    } while (0)
-    // (seed PLANES without a cone -- SEEDED == 1 -- exist for 64-row tiles only: six fused levels, hgi_capi.hip host_banded)
-#define HGI_ENC_ID(I, ID)                                                     \
-    do {                                                                      \
-        if (cone) HGI_ENC(I, ID, 2);                                          \
-        else if (!seeds) HGI_ENC(I, ID, 0);                                   \
-        else if constexpr (TH == 64) HGI_ENC(I, ID, 1);                       \
-        else return hipErrorInvalidValue;                                     \
-    } while (0)
-#define HGI_ENC_I(I)                                                          \
-    do {                                                                      \
-        if (ident) HGI_ENC_ID(I, true); else HGI_ENC_ID(I, false);            \
-    } while (0)
-    if (interp == kInterpCrossed) HGI_ENC_I(kInterpCrossed); else HGI_ENC_I(kInterpLeftTop);
-#undef HGI_ENC_I
-#undef HGI_ENC_ID
-#undef HGI_ENC
-    return hipGetLastError();
+    return with_choices(
+        [&](auto I, auto ID, auto SE) {
+            // (seed PLANES without a cone -- SEEDED == 1 -- exist for 64-row tiles only: six fused levels, hgi_capi.hip host_banded)
+            if constexpr (SE == 1 && TH != 64) return hipErrorInvalidValue;
+            else return launch_tile_kernel<k_enc_tiles<I, ID != 0, SE, TH>>(blocks, lds, s, img, grid, f, k, lut, sd, g, r.aligned);
+        },
+        interp_choice(interp), OneOf<1, 0>{ident ? 1 : 0}, OneOf<2, 0, 1>{cone ? 2 : !seeds ? 0 : 1});
 }
 
 #endif  // HGI_FUSED_ENCODE

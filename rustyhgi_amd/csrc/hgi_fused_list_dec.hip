@@ -83,28 +83,10 @@ hipError_t launch_decode_list(const ListArgs &a, uint32_t max_width, uint32_t k,
     if (seeds && (!cone || k != 4 || seeds->up > (u32)kConeMaxUp || seeds->rec)) return hipErrorInvalidValue;   // (the cone on the frame's own samples only)
     const Seeds sd = seeds ? *seeds : Seeds{nullptr, nullptr, 0, 0, 0, 0};
     const int nh = k >= 2 ? (int)k : 1;
-    // resident tiles per CU: launch_decode_fused's policy, on the list's tile count and its widest frame
-    const int forced = HGI_KNOB(HGI_DEC_WAVES, -1);
-    const u64 tiles = (u64)a.nedge + a.nint;
-    int waves = 0;
-    if (forced >= 0)
-        waves = forced;
-    else if (tiles < 8192)
-        waves = 0;
-    else if (!seeds)
-        waves = max_width > 4096 || k > 4 ? HGI_DEC_STREAM_WAVES_WIDE : k == 1 ? HGI_DEC_STREAM_WAVES_L1 : HGI_DEC_STREAM_WAVES;
-    else
-        waves = tiles >= 65536 ? HGI_DEC_DEEP_WAVES : HGI_DEC_SHALLOW_WAVES;
-    const size_t lds = lds_for_waves((size_t)buf_bytes(nh), waves);
-    const dim3 grid((u32)blocks), b(NL);
-#define HGI_LIST(I, SE) hipLaunchKernelGGL((k_dec_list<I, SE>), grid, b, lds, s, a, k, sd)
-    if (interp == kInterpCrossed) {
-        if (cone) HGI_LIST(kInterpCrossed, 2); else HGI_LIST(kInterpCrossed, 0);
-    } else {
-        if (cone) HGI_LIST(kInterpLeftTop, 2); else HGI_LIST(kInterpLeftTop, 0);
-    }
-#undef HGI_LIST
-    return hipGetLastError();
+    // resident tiles per CU: on the list's tile count and its widest frame
+    const size_t lds = lds_for_waves((size_t)buf_bytes(nh), dec_resident_tiles((u64)a.nedge + a.nint, max_width, k, seeds != nullptr));
+    return with_choices([&](auto I, auto SE) { return launch_tile_kernel<k_dec_list<I, SE>>(dim3((u32)blocks), lds, s, a, k, sd); },
+                        interp_choice(interp), OneOf<2, 0>{cone ? 2 : 0});
 }
 
 }  // namespace hgi

@@ -75,14 +75,6 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(IDENT ? HGI_
     enc_fine_generic<INTERP, IDENT>(buf, rbuf, slut, lc.fr, lc.out, tl, W, H, (lc.aligned & 1u) != 0);
 }
 
-hipError_t list_static_lds_is_empty(const void *kernel)
-{
-    hipFuncAttributes fa;
-    const hipError_t e = hipFuncGetAttributes(&fa, kernel);
-    if (e != hipSuccess) return e;
-    return fa.sharedSizeBytes == 0 ? hipSuccess : hipErrorInvalidDeviceFunction;
-}
-
 }  // namespace
 
 hipError_t launch_encode_list(const ListArgs &a, uint32_t k, int interp, const Lut256 &lut, bool ident, const Seeds *seeds, hipStream_t s)
@@ -94,28 +86,10 @@ hipError_t launch_encode_list(const ListArgs &a, uint32_t k, int interp, const L
     if (seeds && (!cone || k != 4 || seeds->up > (u32)kConeMaxUp || seeds->rec || seeds->q)) return hipErrorInvalidValue;
     const Seeds sd = seeds ? *seeds : Seeds{nullptr, nullptr, 0, 0, 0, 0};
     const int nh = k >= 2 ? (int)k : 1;
-    const int enc_waves = HGI_KNOB(HGI_ENC_WAVES, 0);
-    const size_t lds = lds_for_waves((size_t)buf_bytes(nh) + ((rbuf_bytes(nh) + 15) & ~15) + 256, enc_waves);
-    const dim3 grid((u32)blocks), b(NL);
-#define HGI_LIST(I, ID, SE)                                                                                        \
-    do {                                                                                                           \
-        static const hipError_t lds0 = list_static_lds_is_empty(reinterpret_cast<const void *>(&k_enc_list<I, ID, SE>)); \
-        if (lds0 != hipSuccess) return lds0;                                                                       \
-        hipLaunchKernelGGL((k_enc_list<I, ID, SE>), grid, b, lds, s, a, k, lut, sd);                                 \
-    } while (0)
-#define HGI_LIST_ID(I, ID)                                           \
-    do {                                                             \
-        if (cone) HGI_LIST(I, ID, 2); else HGI_LIST(I, ID, 0);       \
-    } while (0)
-#define HGI_LIST_I(I)                                                \
-    do {                                                             \
-        if (ident) HGI_LIST_ID(I, true); else HGI_LIST_ID(I, false); \
-    } while (0)
-    if (interp == kInterpCrossed) HGI_LIST_I(kInterpCrossed); else HGI_LIST_I(kInterpLeftTop);
-#undef HGI_LIST_I
-#undef HGI_LIST_ID
-#undef HGI_LIST
-    return hipGetLastError();
+    const size_t lds = lds_for_waves(enc_lds_bytes(nh), HGI_KNOB(HGI_ENC_WAVES, 0));
+    return with_choices(
+        [&](auto I, auto ID, auto SE) { return launch_tile_kernel<k_enc_list<I, ID != 0, SE>>(dim3((u32)blocks), lds, s, a, k, lut, sd); },
+        interp_choice(interp), OneOf<1, 0>{ident ? 1 : 0}, OneOf<2, 0>{cone ? 2 : 0});
 }
 
 }  // namespace hgi

@@ -93,28 +93,10 @@ hipError_t launch_decode_pitched(const uint8_t *grid, uint8_t *img, const Pitche
     if (!p.ok) return hipErrorInvalidValue;
     const Seeds sd = seeds ? *seeds : Seeds{nullptr, nullptr, 0, 0, 0, 0};
     const int nh = k >= 2 ? (int)k : 1;
-    // resident tiles per CU: launch_decode_fused's policy, on this launch's tile count
-    const int forced = HGI_KNOB(HGI_DEC_WAVES, -1);
-    const u64 tiles = (u64)p.nf + p.nedge;
-    int waves = 0;
-    if (forced >= 0)
-        waves = forced;
-    else if (tiles < 8192)
-        waves = 0;
-    else if (!seeds)
-        waves = f.width > 4096 || k > 4 ? HGI_DEC_STREAM_WAVES_WIDE : k == 1 ? HGI_DEC_STREAM_WAVES_L1 : HGI_DEC_STREAM_WAVES;
-    else
-        waves = tiles >= 65536 ? HGI_DEC_DEEP_WAVES : HGI_DEC_SHALLOW_WAVES;
-    const size_t lds = lds_for_waves((size_t)buf_bytes(nh), waves);
-    const dim3 blocks((u32)pitched_blocks(p)), b(NL);
-#define HGI_PIT(I, SE) hipLaunchKernelGGL((k_dec_pitched<I, SE>), blocks, b, lds, s, grid, img, k, sd, p)
-    if (interp == kInterpCrossed) {
-        if (cone) HGI_PIT(kInterpCrossed, 2); else HGI_PIT(kInterpCrossed, 0);
-    } else {
-        if (cone) HGI_PIT(kInterpLeftTop, 2); else HGI_PIT(kInterpLeftTop, 0);
-    }
-#undef HGI_PIT
-    return hipGetLastError();
+    const size_t lds = lds_for_waves((size_t)buf_bytes(nh), dec_resident_tiles((u64)p.nf + p.nedge, f.width, k, seeds != nullptr));
+    const dim3 blocks((u32)pitched_blocks(p));
+    return with_choices([&](auto I, auto SE) { return launch_tile_kernel<k_dec_pitched<I, SE>>(blocks, lds, s, grid, img, k, sd, p); },
+                        interp_choice(interp), OneOf<2, 0>{cone ? 2 : 0});
 }
 
 }  // namespace hgi

@@ -84,14 +84,6 @@ __global__ __launch_bounds__(NL) __attribute__((amdgpu_waves_per_eu(IDENT ? HGI_
     enc_fine_generic_pitched<INTERP, IDENT>(buf, rbuf, slut, fr, out, tl, W, H, p.sp, p.dp);
 }
 
-hipError_t pitched_static_lds_is_empty(const void *kernel)
-{
-    hipFuncAttributes fa;
-    const hipError_t e = hipFuncGetAttributes(&fa, kernel);
-    if (e != hipSuccess) return e;
-    return fa.sharedSizeBytes == 0 ? hipSuccess : hipErrorInvalidDeviceFunction;
-}
-
 }  // namespace
 
 hipError_t launch_encode_pitched(const uint8_t *img, uint8_t *grid, const PitchedFrames &f, uint32_t k, int interp, const Lut256 &lut,
@@ -104,29 +96,11 @@ hipError_t launch_encode_pitched(const uint8_t *img, uint8_t *grid, const Pitche
     if (!p.ok) return hipErrorInvalidValue;
     const Seeds sd = seeds ? *seeds : Seeds{nullptr, nullptr, 0, 0, 0, 0};
     const int nh = k >= 2 ? (int)k : 1;
-    const int enc_waves = HGI_KNOB(HGI_ENC_WAVES, 0);
-    const size_t lds = lds_for_waves((size_t)buf_bytes(nh) + ((rbuf_bytes(nh) + 15) & ~15) + 256, enc_waves);
-    const dim3 blocks((u32)pitched_blocks(p)), b(NL);
-    // lut_at() addresses the table from LDS offset 0: checked once per instantiation on the host (launch_encode_fused)
-#define HGI_PIT(I, ID, SE)                                                                                              \
-    do {                                                                                                                \
-        static const hipError_t lds0 = pitched_static_lds_is_empty(reinterpret_cast<const void *>(&k_enc_pitched<I, ID, SE>)); \
-        if (lds0 != hipSuccess) return lds0;                                                                            \
-        hipLaunchKernelGGL((k_enc_pitched<I, ID, SE>), blocks, b, lds, s, img, grid, k, lut, sd, p);                    \
-    } while (0)
-#define HGI_PIT_ID(I, ID)                                          \
-    do {                                                           \
-        if (cone) HGI_PIT(I, ID, 2); else HGI_PIT(I, ID, 0);       \
-    } while (0)
-#define HGI_PIT_I(I)                                               \
-    do {                                                           \
-        if (ident) HGI_PIT_ID(I, true); else HGI_PIT_ID(I, false); \
-    } while (0)
-    if (interp == kInterpCrossed) HGI_PIT_I(kInterpCrossed); else HGI_PIT_I(kInterpLeftTop);
-#undef HGI_PIT_I
-#undef HGI_PIT_ID
-#undef HGI_PIT
-    return hipGetLastError();
+    const size_t lds = lds_for_waves(enc_lds_bytes(nh), HGI_KNOB(HGI_ENC_WAVES, 0));
+    const dim3 blocks((u32)pitched_blocks(p));
+    return with_choices(
+        [&](auto I, auto ID, auto SE) { return launch_tile_kernel<k_enc_pitched<I, ID != 0, SE>>(blocks, lds, s, img, grid, k, lut, sd, p); },
+        interp_choice(interp), OneOf<1, 0>{ident ? 1 : 0}, OneOf<2, 0>{cone ? 2 : 0});
 }
 
 }  // namespace hgi

@@ -19,6 +19,7 @@
 // stride-256 plane (w * h / 65536 points).
 #define HGI_FUSED_NO_LAUNCHERS 1
 #include "hgi_fused_dec.hip"   // the decode direction's build settings and tile procedure, 128 x 64 tiles
+#include "hgi_dec_chain.h"
 
 namespace hgi {
 namespace {
@@ -151,21 +152,8 @@ __device__ __forceinline__ void dec_fine_region(const u8 *buf, __amdgpu_buffer_r
         const u32 he = h0[0], hf = h0[1];
         e16 = last ? he : e16;
         f16 = last ? hf : f16;
-        uint2 c, fl;
-        c.x = __builtin_amdgcn_perm(E.y, E.x, 0x06040200u);
-        c.y = __builtin_amdgcn_perm(E.w, E.z, 0x06040200u);
-        fl.x = __builtin_amdgcn_perm(F.y, F.x, 0x06040200u);
-        fl.y = __builtin_amdgcn_perm(F.w, F.z, 0x06040200u);
-        u32 P0, P1;
-        pred8<INTERP>(c, e16, fl, f16, P0, P1);
-        u32 e0 = E.x, e1 = E.y, e2 = E.z, e3 = E.w, o0 = O.x, o1 = O.y, o2 = O.z, o3 = O.w;
-        HGI_ADDB(e0, 1, P0, 0); HGI_ADDB(e0, 3, P0, 1); HGI_ADDB(e1, 1, P0, 2); HGI_ADDB(e1, 3, P0, 3);
-        HGI_ADDB(e2, 1, P1, 0); HGI_ADDB(e2, 3, P1, 1); HGI_ADDB(e3, 1, P1, 2); HGI_ADDB(e3, 3, P1, 3);
-        HGI_ADDB(o0, 0, P0, 0); HGI_ADDB(o0, 1, P0, 0); HGI_ADDB(o0, 2, P0, 1); HGI_ADDB(o0, 3, P0, 1);
-        HGI_ADDB(o1, 0, P0, 2); HGI_ADDB(o1, 1, P0, 2); HGI_ADDB(o1, 2, P0, 3); HGI_ADDB(o1, 3, P0, 3);
-        HGI_ADDB(o2, 0, P1, 0); HGI_ADDB(o2, 1, P1, 0); HGI_ADDB(o2, 2, P1, 1); HGI_ADDB(o2, 3, P1, 1);
-        HGI_ADDB(o3, 0, P1, 2); HGI_ADDB(o3, 1, P1, 2); HGI_ADDB(o3, 2, P1, 3); HGI_ADDB(o3, 3, P1, 3);
-        v4u r0v = {e0, e1, e2, e3}, r1v = {o0, o1, o2, o3};
+        v4u r0v, r1v;
+        dec_fine_rows<INTERP>(E, F, e16, f16, O, r0v, r1v);
         const int y = 2 * (rp0 + it * (NL / CH));
         const u32 voff = base + (u32)y * pitch + (u32)c16;
         store_rows_window(r0v, r1v, rd, voff, __builtin_amdgcn_readfirstlane(pitch), cl.lo - c16, cl.hi - c16,
@@ -179,23 +167,7 @@ template <int INTERP, int EDGE>
 __device__ __forceinline__ void dec_tile_region(u8 *buf, Tile tl, __amdgpu_buffer_rsrc_t rd, u32 base, u32 pitch, Clip cl,
                                                 const v4u (&odd)[NFINE], u32 k, u32 W, u32 H)
 {
-    const int rows = (int)(H - tl.Y0), cols = (int)(W - tl.X0);
-#define HGI_DEC_REGION_COARSE(SUB)                                 \
-    if (k > HGI_LOG2(SUB)) {                                       \
-        dec_cells<INTERP, EDGE != 0>(buf, SUB, tl, W, H);          \
-        dec_halo_cells<INTERP>(buf, SUB, tl, W, H);                \
-        LDS_ORDER();                                               \
-    }
-    if (MAXK >= 6) HGI_DEC_REGION_COARSE(32)
-    if (MAXK >= 5) HGI_DEC_REGION_COARSE(16)
-    HGI_DEC_REGION_COARSE(8)
-    HGI_DEC_REGION_COARSE(4)
-#undef HGI_DEC_REGION_COARSE
-    if (k >= 2) {
-        dec_level2_fast<INTERP, EDGE>(buf, rows, cols);
-        dec_halo_cells<INTERP>(buf, 2, tl, W, H);
-        LDS_ORDER();
-    }
+    dec_chain<INTERP, EDGE>(buf, tl, k, W, H);
     dec_fine_region<INTERP>(buf, rd, base, pitch, odd, cl);
 }
 
@@ -318,16 +290,13 @@ hipError_t launch_decode_region(const uint8_t *grid, uint8_t *out, const Frames 
     rg.rh = rr.height;
     rg.opitch = rr.out_pitch;
     rg.ostride = rr.out_frame_stride;
-    // the store side: one frame's window addressed with 32 bits (a one-row window never steps by the pitch)
-    const u64 pitch = rr.height > 1 ? rr.out_pitch : rr.width;
-    const u64 span = (u64)(rr.height - 1) * pitch + rr.width;
-    const bool store32 = rr.height == 1 || (pitch < (1ull << 32) && span + 64 < (1ull << 32));
-    if (!store32) {
+    const StoreSide st = store_side_32(rr.height, rr.width, rr.out_pitch);      // one frame's window addressed with 32 bits
+    if (!st.ok) {
         r.aligned &= 1u;                    // every tile through the byte-checked path
         r.g.full_x = r.g.full_y = 0;
     }
-    rg.pitch = store32 ? (u32)pitch : 0u;
-    rg.span = store32 ? (u32)span : 0u;
+    rg.pitch = st.ok ? (u32)st.pitch : 0u;
+    rg.span = st.ok ? (u32)st.span : 0u;
     rg.cx0 = rr.x0 / TW;
     rg.cy0 = rr.y0 / TH;
     const u32 cx1 = (rr.x0 + rr.width - 1) / TW + 1, cy1 = (rr.y0 + rr.height - 1) / TH + 1;
@@ -346,28 +315,10 @@ hipError_t launch_decode_region(const uint8_t *grid, uint8_t *out, const Frames 
     rg.fd_ipf = make_fastdiv(rg.ipf ? rg.ipf : 1u);
     Seeds sd = seeds ? *seeds : Seeds{nullptr, nullptr, 0, 0, 0, 0};
     const int nh = k >= 2 ? (int)k : 1;
-    // resident tiles per CU: launch_decode_fused's policy, on the cover's tile count
-    const int forced = HGI_KNOB(HGI_DEC_WAVES, -1);
-    const u64 tiles = nf + ne;
-    int waves = 0;
-    if (forced >= 0)
-        waves = forced;
-    else if (tiles < 8192)
-        waves = 0;
-    else if (!seeds)
-        waves = f.width > 4096 || k > 4 ? HGI_DEC_STREAM_WAVES_WIDE : k == 1 ? HGI_DEC_STREAM_WAVES_L1 : HGI_DEC_STREAM_WAVES;
-    else
-        waves = tiles >= 65536 ? HGI_DEC_DEEP_WAVES : HGI_DEC_SHALLOW_WAVES;
-    const size_t lds = lds_for_waves((size_t)buf_bytes(nh), waves);
-    const dim3 blocks(((rg.nedge + 7u) & ~7u) + rg.nf), b(NL);
-#define HGI_REG(I, SE) hipLaunchKernelGGL((k_dec_region<I, SE>), blocks, b, lds, s, grid, out, f, k, sd, rg, r.aligned)
-    if (interp == kInterpCrossed) {
-        if (cone) HGI_REG(kInterpCrossed, 2); else HGI_REG(kInterpCrossed, 0);
-    } else {
-        if (cone) HGI_REG(kInterpLeftTop, 2); else HGI_REG(kInterpLeftTop, 0);
-    }
-#undef HGI_REG
-    return hipGetLastError();
+    const size_t lds = lds_for_waves((size_t)buf_bytes(nh), dec_resident_tiles(nf + ne, f.width, k, seeds != nullptr));
+    const dim3 blocks(((rg.nedge + 7u) & ~7u) + rg.nf);
+    return with_choices([&](auto I, auto SE) { return launch_tile_kernel<k_dec_region<I, SE>>(blocks, lds, s, grid, out, f, k, sd, rg, r.aligned); },
+                        interp_choice(interp), OneOf<2, 0>{cone ? 2 : 0});
 }
 
 }  // namespace hgi

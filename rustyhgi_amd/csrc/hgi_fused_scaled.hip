@@ -348,15 +348,12 @@ hipError_t launch_decode_scaled(const uint8_t *src, uint8_t *out, const ScaledVi
     // columns up to its halo columns (TW + 64) plus a chunk's 16 << s bytes
     const u64 rows_max = (u64)sc.ty * TH + 64, cols_max = ((u64)sc.tx * TW + 64 + 16) << v.shift;
     const bool read32 = v.shift < 32 && rows_max * v.row_pitch + cols_max + 64 < (1ull << 32) && v.frame_bytes < (1ull << 32);
-    // the store side: one output frame addressed with 32 bits (a one-row frame never steps by the pitch)
-    const u64 pitch = v.height > 1 ? v.out_pitch : v.width;
-    const u64 span = (u64)(v.height - 1) * pitch + v.width;
-    const bool store32 = v.height == 1 || (pitch < (1ull << 32) && span + 64 < (1ull << 32));
-    const bool fast = read32 && store32 && !HGI_SWITCH(HGI_FORCE_CHECKED);
+    const StoreSide st = store_side_32(v.height, v.width, v.out_pitch);      // one output frame addressed with 32 bits
+    const bool fast = read32 && st.ok && !HGI_SWITCH(HGI_FORCE_CHECKED);
     sc.rp32 = fast ? (u32)v.row_pitch : 0u;
     sc.bytes32 = fast ? (u32)v.frame_bytes : 0u;
-    sc.pitch = fast ? (u32)pitch : 0u;
-    sc.span = fast ? (u32)span : 0u;
+    sc.pitch = fast ? (u32)st.pitch : 0u;
+    sc.span = fast ? (u32)st.span : 0u;
     sc.ix = fast ? v.width / TW : 0u;
     sc.iy = fast ? v.height / TH : 0u;
     // A wide load reads 16 << s bytes for a chunk's 16 view bytes: on the frame's last source row the dword after the row's last
@@ -376,37 +373,12 @@ hipError_t launch_decode_scaled(const uint8_t *src, uint8_t *out, const ScaledVi
     sc.fd_ix = make_fastdiv(sc.ix ? sc.ix : 1u);
     sc.fd_ipf = make_fastdiv(sc.ipf ? sc.ipf : 1u);
     Seeds sd = seeds ? *seeds : Seeds{nullptr, nullptr, 0, 0, 0, 0};
-    // resident tiles per CU: launch_decode_fused's policy, on the view's tile count
-    const int forced = HGI_KNOB(HGI_DEC_WAVES, -1);
-    const u64 tiles = nf + ne;
-    int waves = 0;
-    if (forced >= 0)
-        waves = forced;
-    else if (tiles < 8192)
-        waves = 0;
-    else if (!seeds)
-        waves = v.width > 4096 || k > 4 ? HGI_DEC_STREAM_WAVES_WIDE : k == 1 ? HGI_DEC_STREAM_WAVES_L1 : HGI_DEC_STREAM_WAVES;
-    else
-        waves = tiles >= 65536 ? HGI_DEC_DEEP_WAVES : HGI_DEC_SHALLOW_WAVES;
-    const size_t lds = lds_for_waves((size_t)buf_bytes(nh), waves);
-    const dim3 blocks(((sc.nedge + 7u) & ~7u) + sc.nf), b(NL);
+    const size_t lds = lds_for_waves((size_t)buf_bytes(nh), dec_resident_tiles(nf + ne, v.width, k, seeds != nullptr));
+    const dim3 blocks(((sc.nedge + 7u) & ~7u) + sc.nf);
     const u32 fastu = fast ? 1u : 0u;
-    const int sh = v.shift == 1 ? 1 : v.shift == 2 ? 2 : 0;
-#define HGI_SCL(I, SE, SH) hipLaunchKernelGGL((k_dec_scaled<I, SE, SH>), blocks, b, lds, s, src, out, k, sd, sc, fastu)
-#define HGI_SCL_SH(I, SE)                 \
-    do {                                  \
-        if (sh == 1) HGI_SCL(I, SE, 1);   \
-        else if (sh == 2) HGI_SCL(I, SE, 2); \
-        else HGI_SCL(I, SE, 0);           \
-    } while (0)
-    if (interp == kInterpCrossed) {
-        if (cone) HGI_SCL_SH(kInterpCrossed, 2); else HGI_SCL_SH(kInterpCrossed, 0);
-    } else {
-        if (cone) HGI_SCL_SH(kInterpLeftTop, 2); else HGI_SCL_SH(kInterpLeftTop, 0);
-    }
-#undef HGI_SCL_SH
-#undef HGI_SCL
-    return hipGetLastError();
+    return with_choices(
+        [&](auto I, auto SE, auto SH) { return launch_tile_kernel<k_dec_scaled<I, SE, SH>>(blocks, lds, s, src, out, k, sd, sc, fastu); },
+        interp_choice(interp), OneOf<2, 0>{cone ? 2 : 0}, OneOf<1, 2, 0>{v.shift == 1 ? 1 : v.shift == 2 ? 2 : 0});
 }
 
 }  // namespace hgi

@@ -258,25 +258,16 @@ hipError_t launch_decode_map(const uint8_t *grid, const void *table, void *out, 
     const PitchedPlan &p = mp.p;
     const TileLaunch t = tile_launch(p, k, up);
     if (!t.ok || (elem != 2 && elem != 4)) return hipErrorInvalidValue;
-    // resident tiles per CU: launch_decode_pitched's policy on this launch's tile count, unless this unit was built with a
-    // number of its own
+    // resident tiles per CU: the decoders' policy on this launch's tile count, unless this unit was built with a number of its
+    // own for launches of 8 192 tiles and more
     const u64 tiles = (u64)p.nf + p.nedge;
-    int waves = 0;
-    if (tiles < 8192)
-        waves = 0;
-    else if (HGI_MAP_WAVES > 0)
-        waves = HGI_MAP_WAVES;
-    else if (!t.cone)
-        waves = p.W > 4096 || k > 4 ? HGI_DEC_STREAM_WAVES_WIDE : k == 1 ? HGI_DEC_STREAM_WAVES_L1 : HGI_DEC_STREAM_WAVES;
-    else
-        waves = tiles >= 65536 ? HGI_DEC_DEEP_WAVES : HGI_DEC_SHALLOW_WAVES;
+    const int waves = tiles >= 8192 && HGI_MAP_WAVES > 0 ? HGI_MAP_WAVES : dec_resident_tiles(tiles, p.W, k, t.cone);
     const size_t lds = lds_for_waves((size_t)buf_bytes(t.nh) + 256 * (size_t)elem + kMapStageBytes, waves);   // the decoder's, the table and the staging rows behind it
     const u8 *tab = static_cast<const u8 *>(table);
     u8 *dst = static_cast<u8 *>(out);
     return with_choices(
-        [&](auto I, auto SE, auto EL) { return launch_tile_kernel<k_dec_map<I, SE, EL>>(t, lds, s, grid, tab, dst, k, t.sd, mp); },
-        OneOf<kInterpCrossed, kInterpLeftTop>{interp == kInterpCrossed ? kInterpCrossed : kInterpLeftTop}, OneOf<2, 0>{t.cone ? 2 : 0},
-        OneOf<4, 2>{(int)elem});
+        [&](auto I, auto SE, auto EL) { return launch_tile_kernel<k_dec_map<I, SE, EL>>(t.blocks, lds, s, grid, tab, dst, k, t.sd, mp); },
+        interp_choice(interp), OneOf<2, 0>{t.cone ? 2 : 0}, OneOf<4, 2>{(int)elem});
 }
 
 }  // namespace hgi

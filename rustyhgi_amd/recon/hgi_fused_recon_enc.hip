@@ -222,10 +222,9 @@ hipError_t launch_encode_recon(const uint8_t *img, uint8_t *grid, uint8_t *recon
     if (!t.ok) return hipErrorInvalidValue;
     return with_choices(
         [&](auto I, auto ID, auto SE) {
-            return launch_tile_kernel<k_enc_recon<I, ID != 0, SE>>(t, enc_lds_bytes(t.nh), s, img, grid, recon, k, lut, t.sd, rp);
+            return launch_tile_kernel<k_enc_recon<I, ID != 0, SE>>(t.blocks, enc_lds_bytes(t.nh), s, img, grid, recon, k, lut, t.sd, rp);
         },
-        OneOf<kInterpCrossed, kInterpLeftTop>{interp == kInterpCrossed ? kInterpCrossed : kInterpLeftTop}, OneOf<1, 0>{ident ? 1 : 0},
-        OneOf<2, 0>{t.cone ? 2 : 0});
+        interp_choice(interp), OneOf<1, 0>{ident ? 1 : 0}, OneOf<2, 0>{t.cone ? 2 : 0});
 }
 
 }  // namespace hgi

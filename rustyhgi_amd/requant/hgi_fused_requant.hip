@@ -194,8 +194,8 @@ hipError_t launch_requant(const uint8_t *src, uint8_t *dst, const PitchedPlan &p
     const TileLaunch t = tile_launch(p, k, up);
     if (!t.ok) return hipErrorInvalidValue;
     return with_choices(
-        [&](auto I, auto SE) { return launch_tile_kernel<k_requant<I, SE>>(t, enc_lds_bytes(t.nh), s, src, dst, k, lut, t.sd, p); },
-        OneOf<kInterpCrossed, kInterpLeftTop>{interp == kInterpCrossed ? kInterpCrossed : kInterpLeftTop}, OneOf<2, 0>{t.cone ? 2 : 0});
+        [&](auto I, auto SE) { return launch_tile_kernel<k_requant<I, SE>>(t.blocks, enc_lds_bytes(t.nh), s, src, dst, k, lut, t.sd, p); },
+        interp_choice(interp), OneOf<2, 0>{t.cone ? 2 : 0});
 }
 
 }  // namespace hgi

@@ -419,10 +419,9 @@ hipError_t launch_encode_typed(const void *img, uint8_t *grid, const TypedPlan &
     const u8 *src = static_cast<const u8 *>(img);
     return with_choices(
         [&](auto I, auto ID, auto SE, auto EL) {
-            return launch_tile_kernel<k_enc_typed<I, ID != 0, SE, EL>>(t, enc_lds_bytes(t.nh), s, src, grid, k, lut, t.sd, tp, cv);
+            return launch_tile_kernel<k_enc_typed<I, ID != 0, SE, EL>>(t.blocks, enc_lds_bytes(t.nh), s, src, grid, k, lut, t.sd, tp, cv);
         },
-        OneOf<kInterpCrossed, kInterpLeftTop>{interp == kInterpCrossed ? kInterpCrossed : kInterpLeftTop}, OneOf<1, 0>{ident ? 1 : 0},
-        OneOf<2, 0>{t.cone ? 2 : 0}, OneOf<4, 2>{(int)elem});
+        interp_choice(interp), OneOf<1, 0>{ident ? 1 : 0}, OneOf<2, 0>{t.cone ? 2 : 0}, OneOf<4, 2>{(int)elem});
 }
 
 }  // namespace hgi

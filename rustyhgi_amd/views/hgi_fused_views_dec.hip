@@ -75,19 +75,10 @@ hipError_t launch_views_decode(const ViewArgs &a, uint32_t max_width, uint32_t k
 {
     const TileLaunch t = views_tile_launch(a, k, up);
     if (!t.ok) return hipErrorInvalidValue;
-    // resident tiles per CU: launch_decode_list's policy, on the list's tile count and its widest frame
-    const u64 tiles = (u64)a.nedge + a.nint;
-    int waves = 0;
-    if (tiles < 8192)
-        waves = 0;
-    else if (!t.cone)
-        waves = max_width > 4096 || k > 4 ? HGI_DEC_STREAM_WAVES_WIDE : k == 1 ? HGI_DEC_STREAM_WAVES_L1 : HGI_DEC_STREAM_WAVES;
-    else
-        waves = tiles >= 65536 ? HGI_DEC_DEEP_WAVES : HGI_DEC_SHALLOW_WAVES;
-    const size_t lds = lds_for_waves((size_t)buf_bytes(t.nh), waves);
-    return with_choices([&](auto I, auto SE) { return launch_tile_kernel<k_dec_views<I, SE>>(t, lds, s, a, k, t.sd); },
-                        OneOf<kInterpCrossed, kInterpLeftTop>{interp == kInterpCrossed ? kInterpCrossed : kInterpLeftTop},
-                        OneOf<2, 0>{t.cone ? 2 : 0});
+    // resident tiles per CU: on the list's tile count and its widest frame
+    const size_t lds = lds_for_waves((size_t)buf_bytes(t.nh), dec_resident_tiles((u64)a.nedge + a.nint, max_width, k, t.cone));
+    return with_choices([&](auto I, auto SE) { return launch_tile_kernel<k_dec_views<I, SE>>(t.blocks, lds, s, a, k, t.sd); },
+                        interp_choice(interp), OneOf<2, 0>{t.cone ? 2 : 0});
 }
 
 }  // namespace hgi

@@ -74,9 +74,8 @@ hipError_t launch_views_encode(const ViewArgs &a, uint32_t k, uint32_t up, int i
     const TileLaunch t = views_tile_launch(a, k, up);
     if (!t.ok) return hipErrorInvalidValue;
     return with_choices(
-        [&](auto I, auto ID, auto SE) { return launch_tile_kernel<k_enc_views<I, ID != 0, SE>>(t, enc_lds_bytes(t.nh), s, a, k, lut, t.sd); },
-        OneOf<kInterpCrossed, kInterpLeftTop>{interp == kInterpCrossed ? kInterpCrossed : kInterpLeftTop}, OneOf<1, 0>{ident ? 1 : 0},
-        OneOf<2, 0>{t.cone ? 2 : 0});
+        [&](auto I, auto ID, auto SE) { return launch_tile_kernel<k_enc_views<I, ID != 0, SE>>(t.blocks, enc_lds_bytes(t.nh), s, a, k, lut, t.sd); },
+        interp_choice(interp), OneOf<1, 0>{ident ? 1 : 0}, OneOf<2, 0>{t.cone ? 2 : 0});
 }
 
 }  // namespace hgi

@@ -1,6 +1,6 @@
 """What the CPU suites of the four companion libraries (test_recon.py, test_mapped.py, test_typed.py, test_requant.py) check in
-common about their sources and their build, and the steps they all take: a companion's directory and rustyhgi_amd/companion/,
-which all four include.  `name` is recon, map, typed or requant throughout."""
+common about their sources and their build, and the steps they all take: a companion's directory, rustyhgi_amd/companion/,
+which all four include, and the launch layer of rustyhgi_amd/csrc/ under it.  `name` is recon, map, typed or requant throughout."""
 import importlib
 import os
 import re
@@ -14,6 +14,8 @@ from conftest import ROOT
 
 COMPANION_DIR = os.path.join(ROOT, "rustyhgi_amd", "companion")
 COMPANION_FILES = ["companion.mk", "hgi_entry.h", "hgi_sides.h", "hgi_tile.h"]
+CSRC_DIR = os.path.join(ROOT, "rustyhgi_amd", "csrc")
+LAUNCH_FILES = ["hgi_launch.h", "hgi_launch_policy.h", "hgi_dec_chain.h"]      # what hgi_tile.h takes from csrc/ beside the tile procedure
 KERNEL_UNIT = {"recon": "hgi_fused_recon_enc.hip", "map": "hgi_fused_map_dec.hip", "typed": "hgi_fused_typed_enc.hip",
                "requant": "hgi_fused_requant.hip"}
 ENC_LDS = "(size_t)buf_bytes(nh) + ((rbuf_bytes(nh) + 15) & ~15) + 256"      # the uniform encoder's dynamic LDS, nothing added
@@ -55,8 +57,8 @@ def check_sources(directory, listing=None):
             assert "getenv" not in src and "KNOBS_ENV" not in src and "HGI_KNOB(" not in src, (d, fn)
             assert "hipMalloc" not in src and "hgi_ctx" not in src, (d, fn)      # no device allocation, no ctx
     # the shared headers name no switch either (the `strings` check of each library sees what they compile to)
-    for fn in ("hgi_entry.h", "hgi_sides.h", "hgi_tile.h"):
-        assert not re.search(r'"[^"\n]*HGI_[A-Z0-9_]+[^"\n]*"', open(os.path.join(COMPANION_DIR, fn)).read()), fn
+    for d, fn in [(COMPANION_DIR, f) for f in ("hgi_entry.h", "hgi_sides.h", "hgi_tile.h")] + [(CSRC_DIR, f) for f in LAUNCH_FILES]:
+        assert not re.search(r'"[^"\n]*HGI_[A-Z0-9_]+[^"\n]*"', open(os.path.join(d, fn)).read()), fn
 
 
 def makefile(directory, name, fused):
@@ -73,19 +75,20 @@ def makefile(directory, name, fused):
 
 def unit_source(name, fused):
     """The text of a kernel unit, after what all four have in common: the direction's tile procedure included without its
-    launchers, the shared tile layer behind it, and the launch through it -- launch_tile_kernel makes the static-LDS check of
-    hgi_entry.h once per instantiation.  An encoder-side unit takes its dynamic LDS from enc_lds_bytes, where the uniform
-    encoder's formula stands once."""
+    launchers, the shared tile layer behind it, and the launch through the launch layer that header includes from csrc/ --
+    launch_tile_kernel makes the static-LDS check of hgi_launch.h once per instantiation.  An encoder-side unit takes its dynamic
+    LDS from enc_lds_bytes, where the uniform encoder's formula stands once."""
     src = open(os.path.join(unit_dir(name), KERNEL_UNIT[name])).read()
     assert '#include "../csrc/%s"' % fused in src and '#include "../csrc/hgi_fused_pitched.h"' in src
     assert "#define HGI_FUSED_NO_LAUNCHERS 1" in src
     assert src.index("hgi_fused_pitched.h") < src.index('#include "../companion/hgi_tile.h"')
     assert "launch_tile_kernel<" in src and "hipLaunchKernelGGL" not in src and "#define" not in src[src.index("\nhipError_t launch_"):]
     tile = open(os.path.join(COMPANION_DIR, "hgi_tile.h")).read()
-    entry = open(os.path.join(COMPANION_DIR, "hgi_entry.h")).read()
-    assert '#include "hgi_entry.h"' in tile and "static_lds_is_empty(reinterpret_cast" in tile
-    assert "hipFuncGetAttributes" in entry and "sharedSizeBytes == 0" in entry
-    assert tile.count(ENC_LDS) == 1 and ENC_LDS not in src
+    launch = open(os.path.join(CSRC_DIR, "hgi_launch.h")).read()
+    assert '#include "hgi_entry.h"' in tile and '#include "../csrc/hgi_launch.h"' in tile
+    assert "static_lds_is_empty(reinterpret_cast" in launch
+    assert "hipFuncGetAttributes" in launch and "sharedSizeBytes == 0" in launch
+    assert launch.count(ENC_LDS) == 1 and ENC_LDS not in src and ENC_LDS not in tile
     if fused == "hgi_fused_enc.hip":
         assert "enc_lds_bytes(t.nh)" in src
     return src

@@ -246,9 +246,11 @@ def test_dynamic_lds_of_a_pitched_tile_is_the_uniform_tile():
     """The pitched kernels allocate what the uniform 64-row kernels allocate (the launchers use the same buf_bytes / rbuf_bytes):
     4 848 bytes per decode tile and 7 648 per encode tile at four levels, as DESIGN.md states for the uniform build."""
     src = open(os.path.join(ROOT, "rustyhgi_amd", "csrc", "hgi_fused_pitched_dec.hip")).read()
-    assert "lds_for_waves((size_t)buf_bytes(nh), waves)" in src
+    assert "lds_for_waves((size_t)buf_bytes(nh), dec_resident_tiles(" in src
     src = open(os.path.join(ROOT, "rustyhgi_amd", "csrc", "hgi_fused_pitched_enc.hip")).read()
-    assert "lds_for_waves((size_t)buf_bytes(nh) + ((rbuf_bytes(nh) + 15) & ~15) + 256, enc_waves)" in src
+    assert "lds_for_waves(enc_lds_bytes(nh), HGI_KNOB(HGI_ENC_WAVES, 0))" in src
+    src = open(os.path.join(ROOT, "rustyhgi_amd", "csrc", "hgi_launch.h")).read()
+    assert "enc_lds_bytes(int nh) { return (size_t)buf_bytes(nh) + ((rbuf_bytes(nh) + 15) & ~15) + 256; }" in src
     S, HR, HP, TH, nh = 128, 6, 40, 64, 4
     assert HR * HP + (TH // 2 + nh) * S == 4848
     assert 4848 + ((HR * HP + (TH // 2 + nh) * (S // 2) + 15) & ~15) + 256 == 7648

@@ -172,7 +172,7 @@ def test_recon_unit_is_the_sdwa_build_within_the_encoder_budget(tmp_path):
 
 
 def test_dynamic_lds_is_the_uniform_encoders():
-    """The formula stands once, in companion/hgi_tile.h; the unit's launcher calls it, and the kernel lays the table, `buf` and
+    """The formula stands once, in csrc/hgi_launch.h; the unit's launcher calls it, and the kernel lays the table, `buf` and
     `rbuf` out as the uniform encoder does."""
     src = CL.unit_source("recon", "hgi_fused_enc.hip")
     assert "u8 *buf = smem + 256 - HCOL;" in src and "u8 *rbuf = smem + 256 + buf_bytes(nh) - RCOL;" in src

@@ -123,3 +123,16 @@ def test_fastdiv_is_exact(tmp_path):
                            os.path.join(ROOT, "tests", "cpp", "test_fastdiv.cpp"), "-o", exe])
     p = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0 and " 0 wrong" in p.stdout, p.stdout + p.stderr[-2000:]
+
+
+@pytest.mark.parametrize("stream", (10, 9))
+def test_launch_policy_under_asan_ubsan(tmp_path, stream):
+    """csrc/hgi_launch_policy.h -- the decoders' resident tiles per CU and the LDS padding that holds a launch to them -- is plain
+    C++: the rule against a table written out in tests/cpp/test_launch_policy.cpp, lds_for_waves around its cap.  Once with the
+    header's numbers and once with -DHGI_DEC_STREAM_WAVES=9, as the sweep tools build: the number reaches the rule."""
+    exe = str(tmp_path / "test_launch_policy")
+    flags = [] if stream == 10 else ["-DHGI_DEC_STREAM_WAVES=9", "-DEXPECT_STREAM=9"]
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", *flags, "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=undefined", os.path.join(ROOT, "tests", "cpp", "test_launch_policy.cpp"), "-o", exe])
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0 and "208 cases, 0 failures (plain decode of four levels: %d)" % stream in p.stdout, p.stdout + p.stderr[-4000:]
