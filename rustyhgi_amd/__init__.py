@@ -8,17 +8,21 @@ Decoder.decode_mapped, include/hgi_map.h, and the constants of Encoder.encode_ty
 Encoder.requantize re-codes stored grids with another table in one launch (libhgi_requant.so, include/hgi_requant.h).
 rustyhgi_amd.views (ViewPlan, aligned_arena) plans view lists -- frames with a pitch of their own each -- for Encoder.encode_views /
 Decoder.decode_views: one launch per list (libhgi_views.so, include/hgi_views.h).
+rustyhgi_amd.mviews (MappedViewPlan, padded_batch) plans mapped view lists -- mixed-size grids decoded straight into float16 /
+bfloat16 / float32 frames with a pitch of their own each -- for Decoder.decode_mapped_views: one launch per list
+(libhgi_mviews.so, include/hgi_mviews.h).
 All computation happens in libhgi_hip.so (hand-written HIP kernels); see include/hgi.h.
 """
-from . import entropy, interpolator, mapping, quantizator, views
+from . import entropy, interpolator, mapping, mviews, quantizator, views
 from ._ffi import Context, HgiError, default_context
 from .archive import Archive, Metadata
 from .codec import Decoder, Encoder
 from .grid import Grid
 from .mapping import affine_inverse, affine_table
+from .mviews import MappedViewPlan, padded_batch
 from .planes import Planes
 from .views import ViewPlan, aligned_arena
 
 __all__ = ["Encoder", "Decoder", "Grid", "Archive", "Metadata", "Context", "HgiError", "default_context", "interpolator",
            "quantizator", "entropy", "Planes", "mapping", "affine_table", "affine_inverse", "views", "ViewPlan",
-           "aligned_arena"]
+           "aligned_arena", "mviews", "MappedViewPlan", "padded_batch"]

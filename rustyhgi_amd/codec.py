@@ -929,3 +929,38 @@ class Decoder:
             return out
         _ffi_map.check(st)
         return out
+
+    def decode_mapped_views(self, plan, levels, table):
+        """Decode a MAPPED VIEW LIST: `plan` is a `rustyhgi_amd.mviews.MappedViewPlan` of (grid view, frame view) pairs, all
+        coded with `levels`; every frame view becomes `table[decoded grid view]`, as `decode_mapped` writes it.  `table` is as
+        for `decode_mapped`, of the plan's dtype.  ONE hgi_mviews_decode_dev launch (libhgi_mviews.so), asynchronous on the
+        current stream; a plan or a depth that launch does not serve (HGI_EUNSUPPORTED) is composed from one `decode_mapped`
+        call per view: the same bits.  Returns the destination views."""
+        what = "decode_mapped_views"
+        if len(plan) == 0 or plan.device is None:
+            return list(plan.dsts)
+        import torch
+        from . import _ffi_mviews
+        dtype, esize, _ = _map_table(table, plan.srcs[0], what)
+        if dtype != plan.dtype:
+            raise ValueError("%s: `table` holds %s elements, the plan was made for %s" % (what, dtype, plan.dtype))
+        dev = plan.device.index if plan.device.index is not None else torch.cuda.current_device()
+        if self._ctx is not None and self._ctx.device != dev:      # both routes judge the Decoder's context alike (_bind_ctx)
+            raise ValueError("the views live on cuda:%d but the context was created for cuda:%d" % (dev, self._ctx.device))
+        if not _is_torch(table):
+            table = torch.from_numpy(table).to(plan.device)
+        levels = int(levels)
+        st = _ffi.EUNSUPPORTED
+        if plan.fused:
+            if plan.blob is None:      # only empty views
+                return list(plan.dsts)
+            with torch.cuda.device(dev):
+                st = _ffi_mviews.lib().hgi_mviews_decode_dev(_ffi._vp(torch.cuda.current_stream(dev).cuda_stream or 0), plan.blob.data_ptr(),
+                                                             ctypes.addressof(plan.info), levels, self._interp, table.data_ptr())
+        if st == _ffi.EUNSUPPORTED:      # not served by the one launch: the same bits from one mapped decode per view
+            for s, d in zip(plan.srcs, plan.dsts):
+                if s.numel():
+                    self.decode_mapped(s, levels, table, out=d)
+            return list(plan.dsts)
+        _ffi_mviews.check(st)
+        return list(plan.dsts)
