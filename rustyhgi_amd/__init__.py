@@ -11,9 +11,12 @@ Decoder.decode_views: one launch per list (libhgi_views.so, include/hgi_views.h)
 rustyhgi_amd.mviews (MappedViewPlan, padded_batch) plans mapped view lists -- mixed-size grids decoded straight into float16 /
 bfloat16 / float32 frames with a pitch of their own each -- for Decoder.decode_mapped_views: one launch per list
 (libhgi_mviews.so, include/hgi_mviews.h).
+rustyhgi_amd.tviews (TypedViewPlan) plans typed view lists -- mixed-size float16 / bfloat16 / float32 frames with a pitch of
+their own each, encoded straight into grids -- for Encoder.encode_typed_views: one launch per list (libhgi_tviews.so,
+include/hgi_tviews.h).
 All computation happens in libhgi_hip.so (hand-written HIP kernels); see include/hgi.h.
 """
-from . import entropy, interpolator, mapping, mviews, quantizator, views
+from . import entropy, interpolator, mapping, mviews, quantizator, tviews, views
 from ._ffi import Context, HgiError, default_context
 from .archive import Archive, Metadata
 from .codec import Decoder, Encoder
@@ -21,8 +24,9 @@ from .grid import Grid
 from .mapping import affine_inverse, affine_table
 from .mviews import MappedViewPlan, padded_batch
 from .planes import Planes
+from .tviews import TypedViewPlan
 from .views import ViewPlan, aligned_arena
 
 __all__ = ["Encoder", "Decoder", "Grid", "Archive", "Metadata", "Context", "HgiError", "default_context", "interpolator",
            "quantizator", "entropy", "Planes", "mapping", "affine_table", "affine_inverse", "views", "ViewPlan",
-           "aligned_arena", "mviews", "MappedViewPlan", "padded_batch"]
+           "aligned_arena", "mviews", "MappedViewPlan", "padded_batch", "tviews", "TypedViewPlan"]

@@ -633,6 +633,42 @@ class Encoder:
             lambda stream, blob, info: _ffi_views.lib().hgi_views_encode_dev(stream, blob, info, levels, interp, lut),
             lambda ctx, v: _ffi.lib().hgi_encode_u8_pitched_dev(ctx.handle, v[0], v[4], v[2], v[3], levels, interp, lut, v[1], v[5], 1, 0, 0))
 
+    def encode_typed_views(self, plan, scale=255.0, bias=0.0):
+        """Encode a TYPED VIEW LIST: `plan` is a `rustyhgi_amd.tviews.TypedViewPlan` of (float frame view, grid view) pairs --
+        every pair with a shape and two row pitches of its own.  Each destination view, read through its pitch, is bit for bit
+        `encode_typed` of its source view alone under `scale` and `bias`; only the W-byte rows of the destinations are written.
+        ONE hgi_tviews_encode_dev launch (libhgi_tviews.so), asynchronous on the current stream and capturable into a graph; the
+        plan may be launched any number of times.  A plan or a depth that launch does not serve (HGI_EUNSUPPORTED) is composed
+        from one `encode_typed` call per view: the same bytes.  Returns the destination views; empty plans need no device."""
+        what = "encode_typed_views"
+        with np.errstate(over="ignore"):
+            scale, bias = np.float32(scale), np.float32(bias)
+        if not (np.isfinite(scale) and np.isfinite(bias)):
+            raise ValueError("%s: `scale` and `bias` must be finite float32 values" % what)
+        if len(plan) == 0 or plan.device is None:
+            return list(plan.dsts)
+        import torch
+        from . import _ffi_tviews
+        dev = plan.device.index if plan.device.index is not None else torch.cuda.current_device()
+        if self._ctx is not None and self._ctx.device != dev:      # both routes judge the Encoder's context alike (_bind_ctx)
+            raise ValueError("the views live on cuda:%d but the context was created for cuda:%d" % (dev, self._ctx.device))
+        st = _ffi.EUNSUPPORTED
+        if plan.fused:
+            if plan.blob is None:      # only empty views
+                return list(plan.dsts)
+            kind = 1 if plan.dtype == torch.bfloat16 else 0
+            with torch.cuda.device(dev):
+                st = _ffi_tviews.lib().hgi_tviews_encode_dev(
+                    _ffi._vp(torch.cuda.current_stream(dev).cuda_stream or 0), plan.blob.data_ptr(), ctypes.addressof(plan.info), kind,
+                    float(scale), float(bias), self.scale_level, self._interp, self._lut.ctypes.data)
+        if st == _ffi.EUNSUPPORTED:      # not served by the one launch: the same bytes from one typed encode per view
+            for s, d in zip(plan.srcs, plan.dsts):
+                if s.numel():
+                    self.encode_typed(s, float(scale), float(bias), out=d)
+            return list(plan.dsts)
+        _ffi_tviews.check(st)
+        return list(plan.dsts)
+
     def encode_list(self, images, out=None):
         """A list of (h_i, w_i) uint8 frames of any shapes -> the list of their residual planes.  CUDA tensors (one device,
         contiguous): ONE hgi_encode_u8_list_dev call, asynchronous on the current stream, the outputs (h_i, w_i) views into one
