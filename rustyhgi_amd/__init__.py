@@ -14,6 +14,8 @@ bfloat16 / float32 frames with a pitch of their own each -- for Decoder.decode_m
 rustyhgi_amd.tviews (TypedViewPlan) plans typed view lists -- mixed-size float16 / bfloat16 / float32 frames with a pitch of
 their own each, encoded straight into grids -- for Encoder.encode_typed_views: one launch per list (libhgi_tviews.so,
 include/hgi_tviews.h).
+Encoder.requantize_views re-codes a view list of stored grids -- a ViewPlan of (source grid, destination grid) pairs, the plan
+of the view lists unchanged -- with another table: one launch per list (libhgi_qviews.so, include/hgi_qviews.h).
 All computation happens in libhgi_hip.so (hand-written HIP kernels); see include/hgi.h.
 """
 from . import entropy, interpolator, mapping, mviews, quantizator, tviews, views

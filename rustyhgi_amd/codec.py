@@ -342,10 +342,10 @@ def _map_table(table, grids, what):
     return table.dtype, esize, (table.ctypes.data, table.ctypes.data + 256 * esize)
 
 
-def _views_launch(plan, ctx, fused, each):
+def _views_launch(plan, ctx, fused, each, check=None):
     """One view-list call on plan.device: `fused(stream, d_plan, info)` -> status of the one launch; `each(ctx, view layout)` ->
-    status of one pitched call, composed per view when the plan or the launch is not served (HGI_EUNSUPPORTED).  Returns the
-    plan's destination views."""
+    status of one pitched call, composed per view when the plan or the launch is not served (HGI_EUNSUPPORTED).  `check`: what
+    raises for a launch status of another library than libhgi_views.so.  Returns the plan's destination views."""
     import torch
     from . import _ffi_views
     if len(plan) == 0 or plan.device is None:
@@ -365,7 +365,7 @@ def _views_launch(plan, ctx, fused, each):
             if lay[2] and lay[3]:
                 _ffi.check(each(bound, lay))
         return list(plan.dsts)
-    _ffi_views.check(st)
+    (check or _ffi_views.check)(st)
     return list(plan.dsts)
 
 
@@ -557,6 +557,34 @@ class Encoder:
             return out
         _ffi_requant.check(st)
         return out
+
+    def requantize_views(self, plan):
+        """Re-code a VIEW LIST of stored grids with this encoder's table: `plan` is a `rustyhgi_amd.views.ViewPlan` of (source
+        grid view, destination grid view) pairs -- every pair with a shape and two row pitches of its own; a plan that served
+        `encode_views` or `decode_views` serves here unchanged.  Each destination view, read through its pitch, is bit for bit
+        `requantize` of its source view alone; only the W-byte rows of the destinations are written, the sources are not
+        modified.  ONE hgi_qviews_requant_dev launch (libhgi_qviews.so), asynchronous on the current stream and capturable into
+        a graph -- 2 B/px where `decode_views` into a uint8 arena + `encode_views` moves 4 B/px; the plan may be launched any
+        number of times.  What that launch does not serve (HGI_EUNSUPPORTED: 0 or more than 8 levels, or a plan that is not
+        fused) is composed from one `requantize(src, out=dst)` per view: the same bytes.  Under the identity table the result
+        is the source, and the rows are copied per view without a call of the library.  Returns the destination views; empty
+        plans need no device."""
+        from . import _ffi_qviews
+        lut, levels, interp = self._lut.ctypes.data, self.scale_level, self._interp
+        pairs = dict((lay, (s, d)) for lay, s, d in zip(plan.layouts, plan.srcs, plan.dsts) if lay[2] and lay[3])
+
+        def fused(stream, blob, info):
+            if 0 <= levels <= 31 and bool((self._lut == np.arange(256, dtype=np.uint8)).all()):
+                for s, d in pairs.values():      # (`requantize` says why the source is the result at any depth)
+                    d.copy_(s)
+                return _ffi.OK
+            return _ffi_qviews.lib().hgi_qviews_requant_dev(stream, blob, info, levels, interp, lut)
+
+        def each(ctx, v):
+            self.requantize(pairs[v][0], out=pairs[v][1])
+            return _ffi.OK
+
+        return _views_launch(plan, self._ctx, fused, each, check=_ffi_qviews.check)
 
     def encode_typed(self, frames, scale=255.0, bias=0.0, out=None):
         """Encode float frames where they lie: a (H, W) or (B, H, W) torch CUDA tensor of float16, bfloat16 or float32 -- a view
