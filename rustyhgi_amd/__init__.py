@@ -16,9 +16,12 @@ their own each, encoded straight into grids -- for Encoder.encode_typed_views: o
 include/hgi_tviews.h).
 Encoder.requantize_views re-codes a view list of stored grids -- a ViewPlan of (source grid, destination grid) pairs, the plan
 of the view lists unchanged -- with another table: one launch per list (libhgi_qviews.so, include/hgi_qviews.h).
+rustyhgi_amd.sviews (ScaledViewPlan, scaled_shape) plans scaled view lists -- mixed-size stored grids decoded at 1 / 2**shift
+resolution, each through pitches of its own -- for Decoder.decode_scaled_views: one launch per list (libhgi_sviews.so,
+include/hgi_sviews.h).
 All computation happens in libhgi_hip.so (hand-written HIP kernels); see include/hgi.h.
 """
-from . import entropy, interpolator, mapping, mviews, quantizator, tviews, views
+from . import entropy, interpolator, mapping, mviews, quantizator, sviews, tviews, views
 from ._ffi import Context, HgiError, default_context
 from .archive import Archive, Metadata
 from .codec import Decoder, Encoder
@@ -26,9 +29,11 @@ from .grid import Grid
 from .mapping import affine_inverse, affine_table
 from .mviews import MappedViewPlan, padded_batch
 from .planes import Planes
+from .sviews import ScaledViewPlan, scaled_shape
 from .tviews import TypedViewPlan
 from .views import ViewPlan, aligned_arena
 
 __all__ = ["Encoder", "Decoder", "Grid", "Archive", "Metadata", "Context", "HgiError", "default_context", "interpolator",
            "quantizator", "entropy", "Planes", "mapping", "affine_table", "affine_inverse", "views", "ViewPlan",
-           "aligned_arena", "mviews", "MappedViewPlan", "padded_batch", "tviews", "TypedViewPlan"]
+           "aligned_arena", "mviews", "MappedViewPlan", "padded_batch", "tviews", "TypedViewPlan", "sviews",
+           "ScaledViewPlan", "scaled_shape"]

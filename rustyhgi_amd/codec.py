@@ -916,6 +916,40 @@ class Decoder:
             lambda stream, blob, info: _ffi_views.lib().hgi_views_decode_dev(stream, blob, info, levels, interp),
             lambda ctx, v: _ffi.lib().hgi_decode_u8_pitched_dev(ctx.handle, v[0], v[4], v[2], v[3], levels, interp, v[1], v[5], 1, 0, 0))
 
+    def decode_scaled_views(self, plan, levels):
+        """Decode a SCALED VIEW LIST: `plan` is a `rustyhgi_amd.sviews.ScaledViewPlan` of (grid view, image view) pairs, all
+        coded with `levels`; every image view becomes `decode(grid view, levels)[::2**shift, ::2**shift]`, bit for bit, shift
+        being the plan's.  ONE hgi_sviews_decode_dev launch (libhgi_sviews.so), asynchronous on the current stream; a plan or a
+        depth that launch does not serve (HGI_EUNSUPPORTED: shift 0, levels <= shift, nine and more levels left above the
+        lattice, an entry beyond the 32-bit buffer path) is composed from one hgi_decode_scaled_u8_dev call per view, into the
+        destination's pitch, from the grid view itself when its rows are packed and from a packed copy otherwise: the same
+        bytes.  Empty plans need no device.  Returns the destination views."""
+        if len(plan) == 0 or plan.device is None:
+            return list(plan.dsts)
+        import torch
+        from . import _ffi_sviews
+        levels = int(levels)
+        dev = plan.device.index if plan.device.index is not None else torch.cuda.current_device()
+        if self._ctx is not None and self._ctx.device != dev:      # both routes judge the Decoder's context alike (_bind_ctx)
+            raise ValueError("the views live on cuda:%d but the context was created for cuda:%d" % (dev, self._ctx.device))
+        st = _ffi.EUNSUPPORTED
+        if plan.fused:
+            if plan.blob is None:      # only empty views
+                return list(plan.dsts)
+            with torch.cuda.device(dev):
+                st = _ffi_sviews.lib().hgi_sviews_decode_dev(_ffi._vp(torch.cuda.current_stream(dev).cuda_stream or 0), plan.blob.data_ptr(),
+                                                             ctypes.addressof(plan.info), levels, self._interp)
+        if st == _ffi.EUNSUPPORTED:      # not served by the one launch: the same bytes from one scaled decode per view
+            bound = _bind_ctx(plan.srcs[0], self._ctx)
+            for s, (_, dst, w, h, sp, dp) in zip(plan.srcs, plan.layouts):
+                if w and h:
+                    g = s if h == 1 or sp == w else s.contiguous()
+                    _ffi.check(_ffi.lib().hgi_decode_scaled_u8_dev(bound.handle, g.data_ptr(), w, h, levels, self._interp, plan.shift,
+                                                                   dst, dp, 1, 0, 0))
+            return list(plan.dsts)
+        _ffi_sviews.check(st)
+        return list(plan.dsts)
+
     def decode_mapped(self, grids, levels, table, out=None):
         """Decode a view of grids straight into frames of the `table`'s dtype: `out[..., y, x] = table[decoded[..., y, x]]`,
         `decoded` being `decode_view(grids, levels)` -- float16 / bfloat16 / float32 frames, normalised however the table says
