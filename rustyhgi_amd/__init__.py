@@ -19,9 +19,12 @@ of the view lists unchanged -- with another table: one launch per list (libhgi_q
 rustyhgi_amd.sviews (ScaledViewPlan, scaled_shape) plans scaled view lists -- mixed-size stored grids decoded at 1 / 2**shift
 resolution, each through pitches of its own -- for Decoder.decode_scaled_views: one launch per list (libhgi_sviews.so,
 include/hgi_sviews.h).
+rustyhgi_amd.rviews (ReconViewPlan) plans recon view lists -- mixed-size frames encoded into grids and into the images the
+decoder will make of them, each through three pitches of its own -- for Encoder.encode_views_with_reconstruction: one launch
+per list (libhgi_rviews.so, include/hgi_rviews.h).
 All computation happens in libhgi_hip.so (hand-written HIP kernels); see include/hgi.h.
 """
-from . import entropy, interpolator, mapping, mviews, quantizator, sviews, tviews, views
+from . import entropy, interpolator, mapping, mviews, quantizator, rviews, sviews, tviews, views
 from ._ffi import Context, HgiError, default_context
 from .archive import Archive, Metadata
 from .codec import Decoder, Encoder
@@ -29,6 +32,7 @@ from .grid import Grid
 from .mapping import affine_inverse, affine_table
 from .mviews import MappedViewPlan, padded_batch
 from .planes import Planes
+from .rviews import ReconViewPlan
 from .sviews import ScaledViewPlan, scaled_shape
 from .tviews import TypedViewPlan
 from .views import ViewPlan, aligned_arena
@@ -36,4 +40,4 @@ from .views import ViewPlan, aligned_arena
 __all__ = ["Encoder", "Decoder", "Grid", "Archive", "Metadata", "Context", "HgiError", "default_context", "interpolator",
            "quantizator", "entropy", "Planes", "mapping", "affine_table", "affine_inverse", "views", "ViewPlan",
            "aligned_arena", "mviews", "MappedViewPlan", "padded_batch", "tviews", "TypedViewPlan", "sviews",
-           "ScaledViewPlan", "scaled_shape"]
+           "ScaledViewPlan", "scaled_shape", "rviews", "ReconViewPlan"]

@@ -661,6 +661,40 @@ class Encoder:
             lambda stream, blob, info: _ffi_views.lib().hgi_views_encode_dev(stream, blob, info, levels, interp, lut),
             lambda ctx, v: _ffi.lib().hgi_encode_u8_pitched_dev(ctx.handle, v[0], v[4], v[2], v[3], levels, interp, lut, v[1], v[5], 1, 0, 0))
 
+    def encode_views_with_reconstruction(self, plan):
+        """Encode a RECON VIEW LIST: `plan` is a `rustyhgi_amd.rviews.ReconViewPlan` of (image view, grid view, reconstruction
+        view) triples -- every triple with a shape and three row pitches of its own.  Each grid view, read through its pitch, is
+        bit for bit `encode_view` of its source view alone and each reconstruction view bit for bit `Decoder.decode_view` of that
+        grid; only the W-byte rows of the two outputs are written, the sources are not modified.  ONE hgi_rviews_encode_dev
+        launch (libhgi_rviews.so), asynchronous on the current stream and capturable into a graph -- 3 B/px where `encode_views`
+        + `decode_views` move 4 B/px; the plan may be launched any number of times.  What that launch does not serve
+        (HGI_EUNSUPPORTED: 0 or more than 8 levels, or a plan that is not fused) is composed from one
+        `encode_with_reconstruction(src, out=grid, recon=recon)` per view: the same bytes.  Returns `(grid views, recon views)`;
+        empty plans need no device."""
+        done = (list(plan.grids), list(plan.recons))
+        if len(plan) == 0 or plan.device is None:
+            return done
+        import torch
+        from . import _ffi_rviews
+        dev = plan.device.index if plan.device.index is not None else torch.cuda.current_device()
+        if self._ctx is not None and self._ctx.device != dev:      # both routes judge the Encoder's context alike (_bind_ctx)
+            raise ValueError("the views live on cuda:%d but the context was created for cuda:%d" % (dev, self._ctx.device))
+        st = _ffi.EUNSUPPORTED
+        if plan.fused:
+            if plan.blob is None:      # only empty views
+                return done
+            with torch.cuda.device(dev):
+                st = _ffi_rviews.lib().hgi_rviews_encode_dev(
+                    _ffi._vp(torch.cuda.current_stream(dev).cuda_stream or 0), plan.blob.data_ptr(), ctypes.addressof(plan.info),
+                    self.scale_level, self._interp, self._lut.ctypes.data)
+        if st == _ffi.EUNSUPPORTED:      # not served by the one launch: the same bytes from one encode with reconstruction per view
+            for s, g, r in zip(plan.srcs, plan.grids, plan.recons):
+                if s.numel():
+                    self.encode_with_reconstruction(s, out=g, recon=r)
+            return done
+        _ffi_rviews.check(st)
+        return done
+
     def encode_typed_views(self, plan, scale=255.0, bias=0.0):
         """Encode a TYPED VIEW LIST: `plan` is a `rustyhgi_amd.tviews.TypedViewPlan` of (float frame view, grid view) pairs --
         every pair with a shape and two row pitches of its own.  Each destination view, read through its pitch, is bit for bit
